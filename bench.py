@@ -18,6 +18,12 @@ the north-star target (>=1e10 marker-ops/s at >=50 % HBM roofline on one MI355X,
 global problem is z-slab decomposed over N ranks (strong scaling).  --config cfg2/cfg3/
 cfg5 select the other BASELINE configs.
 
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs if
+--dump-outputs DIR is given, and prints the line: metric, value, ms_per_step and the
+configuration.  --full adds what takes runs of its own after (or checks before) the timed
+steps: the per-phase breakdown, the sweep kernels alone, the roofline and LDS-atomic
+records, the CPU baseline (unless --no-cpu-baseline) and the N > 1 overlap self-check.
+
 Prints ONE JSON line (rank 0).
 """
 from __future__ import annotations
@@ -251,6 +257,30 @@ def cpu_baseline(cfg, kernel, seconds_target=15.0):
                       f"sample, not cfg4 itself: the oracle's cost is per marker, independent of the grid"}
 
 
+DUMP_SAMPLE = 1 << 20  # entries kept of a dumped array (8 MB as f64; at most five arrays a run)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(directory, arrays, suffix="", sample=DUMP_SAMPLE):
+    """--dump-outputs DIR: what the last timed step handed its caller, as DIR/<name><suffix>.npy
+    (f64).  `arrays` maps a name to a tensor, or to a list of tensors that are flattened and
+    joined (a level's patch arrays).  An array of more than `sample` entries (DUMP_SAMPLE, over
+    N ranks DUMP_SAMPLE / N each: at most 40 MB a run) is cut to a fixed sample of its
+    entries: ascending indices drawn with DUMP_SEED from the array's size alone, so two builds
+    run with the same arguments write the same entries."""
+    import numpy as np
+    import torch
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, t in arrays.items():
+        flat = torch.cat([p.reshape(-1) for p in t]) if isinstance(t, (list, tuple)) else t.reshape(-1)
+        n = flat.numel()
+        if n > sample:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=sample))
+            flat = flat.index_select(0, torch.from_numpy(idx).to(flat.device))
+        np.save(out / f"{name}{suffix}.npy", flat.to(torch.float64).cpu().numpy())
+
+
 def level_lists(X, N, P, g):
     """LIndexSetData's per-patch lists on a level of P^3 equal patches tiling a
     periodic [0,1)^3 in torch ops -- the check for ibtk_le_level_index_lists, which the
@@ -338,6 +368,49 @@ KERNEL_NOTE = ("interp = k_interp_sweep<K, LVL>; spread = k_spread_sweep<K, LVL,
                "skipped on the device when the re-binning changed nothing) is outside these events")
 
 
+def level_breakdown(args, ctx, step, interp, zero_spread, E, acc, M, entries, S_touched, f):
+    """--full, after the timed steps of run_level: the per-phase breakdown (separate
+    instrumented steps), the sweep kernels alone and the roofline record."""
+    import torch
+    for _ in range(max(3, min(args.steps, 10))):
+        step(True)
+        torch.cuda.synchronize()
+        acc["fill"].append(E[0].elapsed_time(E[1]))
+        if args.move:  # E1-E2 interp, E2-E3 update + lists + bin
+            acc["interp"].append(E[1].elapsed_time(E[2]))
+            acc["bin"].append(E[2].elapsed_time(E[3]))
+        else:
+            acc["bin"].append(E[1].elapsed_time(E[2]))
+            acc["interp"].append(E[2].elapsed_time(E[3]))
+        acc["zero"].append(E[3].elapsed_time(E[4]))
+        acc["spread"].append(E[4].elapsed_time(E[5]))
+    ctx.enable_timing(True)
+    kt = {"interp": [], "spread": []}
+    for _ in range(3):
+        interp()
+        ctx.synchronize()
+        kt["interp"].append(ctx.last_kernel_ms())
+        zero_spread()
+        ctx.synchronize()
+        kt["spread"].append(ctx.last_kernel_ms())
+    ctx.enable_timing(False)
+    mean = lambda v: sum(v) / len(v)
+    k_i, k_s = mean(kt["interp"]), mean(kt["spread"])
+    lds = lds_atomic(ctx, zero_spread, k_s)
+    # per entry X and Q/F (24 + 24 B), per touched point 8 B (interp) or 16 B (spread);
+    # the touched points are those of the ghost-box lists (an upper bound for interp's)
+    B_i = M * 48 + 8 * sum(S_touched)
+    # the spread into the zeroed f (one sweep) writes every point of f and reads none
+    B_s = entries * 48 + 8 * sum(a.numel() for per in f for a in per)
+    dominant = "spread" if k_s >= k_i else "interp"
+    achieved = (B_s / (k_s * 1e-3) if dominant == "spread" else B_i / (k_i * 1e-3)) / 1e9
+    roofline = {"bound": "hbm", "kernel": dominant, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS, "traffic": None,
+                "algorithmic_bytes": {"interp": B_i, "spread": B_s}, "kernel_ms": {"interp": k_i, "spread": k_s},
+                "kernel_note": KERNEL_NOTE, "lds_atomic": lds}
+    return roofline, {k: mean(v) for k, v in acc.items()}
+
+
 def run_level(args, cfg, kernel, dev):
     """--config cfg5 (default): the clustered markers on a multi-patch finest level,
     8^3 patches of 64^3, one launch per sweep over every patch.
@@ -390,9 +463,10 @@ def run_level(args, cfg, kernel, dev):
         for a in per:
             a.uniform_(-1.0, 1.0, generator=gen)
     f = le.alloc_level(geoms, "side", device=dev)
-    # algorithmic bytes: the distinct points each patch's ghost-box stencils touch
-    S_touched = [0, 0, 0]
-    for q, geom in enumerate(geoms):
+    # algorithmic bytes (--full, for the roofline): the distinct points each patch's
+    # ghost-box stencils touch
+    S_touched = [0, 0, 0] if args.full else None
+    for q, geom in enumerate(geoms if args.full else []):
         if os_[q + 1] == os_[q]:
             continue
         idx_q = si[os_[q]:os_[q + 1]].contiguous()
@@ -544,38 +618,17 @@ def run_level(args, cfg, kernel, dev):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     timed_binning = dict(binning)
-    for _ in range(max(3, min(args.steps, 10))):
-        step(True)
-        torch.cuda.synchronize()
-        acc["fill"].append(E[0].elapsed_time(E[1]))
-        if args.move:  # E1-E2 interp, E2-E3 update + lists + bin
-            acc["interp"].append(E[1].elapsed_time(E[2]))
-            acc["bin"].append(E[2].elapsed_time(E[3]))
-        else:
-            acc["bin"].append(E[1].elapsed_time(E[2]))
-            acc["interp"].append(E[2].elapsed_time(E[3]))
-        acc["zero"].append(E[3].elapsed_time(E[4]))
-        acc["spread"].append(E[4].elapsed_time(E[5]))
-    ctx.enable_timing(True)
-    kt = {"interp": [], "spread": []}
-    for _ in range(3):
-        interp()
-        ctx.synchronize()
-        kt["interp"].append(ctx.last_kernel_ms())
-        zero_spread(f)
-        ctx.synchronize()
-        kt["spread"].append(ctx.last_kernel_ms())
-    ctx.enable_timing(False)
-    mean = lambda v: sum(v) / len(v)
-    k_i, k_s = mean(kt["interp"]), mean(kt["spread"])
-    lds = lds_atomic(ctx, lambda: zero_spread(f), k_s)
-    # per entry X and Q/F (24 + 24 B), per touched point 8 B (interp) or 16 B (spread);
-    # the touched points are those of the ghost-box lists (an upper bound for interp's)
-    B_i = M * 48 + 8 * sum(S_touched)
-    # the spread into the zeroed f (one sweep) writes every point of f and reads none
-    B_s = os_[-1] * 48 + 8 * sum(a.numel() for per in f for a in per)
-    dominant = "spread" if k_s >= k_i else "interp"
-    achieved = (B_s / (k_s * 1e-3) if dominant == "spread" else B_i / (k_i * 1e-3)) / 1e9
+    if args.dump_outputs:
+        # what the last timed step handed back: U = J u, f = S F (each component's patch
+        # arrays joined in patch order) and, moving, the updated positions
+        arrays = {"U": U, **{f"f{a}": [per[a] for per in f] for a in range(3)}}
+        if args.move:
+            arrays["X"] = X
+        dump_outputs(args.dump_outputs, arrays)
+    roofline = breakdown = None
+    if args.full:
+        roofline, breakdown = level_breakdown(args, ctx, step, interp, lambda: zero_spread(f), E, acc,
+                                              M, os_[-1], S_touched, f)
     return {
         "metric": METRIC, "value": 2.0 * M * args.steps / elapsed, "unit": "marker-ops/s", "n_gpus": 1,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
@@ -600,12 +653,11 @@ def run_level(args, cfg, kernel, dev):
                             " + zero f and spread(3 comps) in one launch (ibtk_le_level_zero_spread); stationary markers, "
                             "per-patch lists built once at setup (LIndexSetData between regrids), one launch per sweep over "
                             "the 512 patches")},
-        "roofline": {"bound": "hbm", "kernel": dominant, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": None,
-                     "algorithmic_bytes": {"interp": B_i, "spread": B_s}, "kernel_ms": {"interp": k_i, "spread": k_s},
-                     "kernel_note": KERNEL_NOTE, "lds_atomic": lds},
+        # --full only: the roofline, the per-phase breakdown, the touched points, the CPU baseline
+        "full": args.full,
+        "roofline": roofline,
         "cpu_baseline": None,
-        "breakdown_ms": {k: mean(v) for k, v in acc.items()},
+        "breakdown_ms": breakdown,
         "touched_points": S_touched,
     }
 
@@ -669,7 +721,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="cfg4", choices=sorted(CONFIGS))
     ap.add_argument("--kernel", default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also everything beside the headline figure: the per-phase "
+                         "breakdown and the sweep kernels alone (instrumented steps of their own), the roofline "
+                         "and LDS-atomic records (touched points counted at setup), the CPU baseline, and at "
+                         "N > 1 the overlap self-check before the timed steps; a run without it sets up, warms "
+                         "up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last of them computed (U = J u, f = S F by "
+                         "component, with --move the positions X) as DIR/<name>.npy in f64; an array of more than "
+                         "2^20 entries as a fixed seeded sample of its entries (N > 1: <name>_rank<r>.npy, 2^20 / N "
+                         "entries)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--unfused-zero", action="store_true",
                     help="zero f's ghosts (cfg5: all of f) and spread as two launches instead of one "
                          "(ibtk_le_zero_ghosts_spread / ibtk_le_level_zero_spread; A/B)")
@@ -749,7 +812,7 @@ def main():
 
     if cfg.get("patches") and not args.single_patch and world == 1:
         out = run_level(args, cfg, kernel, dev)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(cfg, kernel, args.cpu_seconds)
             except Exception as e:  # the baseline must never hide the GPU result
@@ -866,10 +929,13 @@ def main():
         cur.update(X=Xa, F=Fa, U=Ua)
 
     bin_step()
-    # exact algorithmic bytes: distinct side points touched by the clipped stencils
-    masks = le.mark_stencils(ctx, bins, kernel, "side", geom, cur["X"])
-    S_touched = [int(m.sum(dtype=torch.int64).item()) for m in masks]
-    del masks
+    # exact algorithmic bytes (--full, for the roofline): distinct side points touched by
+    # the clipped stencils
+    S_touched = None
+    if args.full:
+        masks = le.mark_stencils(ctx, bins, kernel, "side", geom, cur["X"])
+        S_touched = [int(m.sum(dtype=torch.int64).item()) for m in masks]
+        del masks
     torch.cuda.synchronize()
     M_total = M_local
     if world > 1:
@@ -1032,9 +1098,9 @@ def main():
     # steps: the overlapped exchanges (interior sweep items running while the ghost
     # planes are in flight on the communicator's stream) must give the bits of the
     # sequential form on every rank; if they do not, the timed steps use the
-    # sequential exchange (and the record says so)
+    # sequential exchange (and the record says so).  A check beside the figure: --full
     overlap_check = None
-    if world > 1 and not args.no_overlap and gm is None:
+    if args.full and world > 1 and not args.no_overlap and gm is None:
         Xb = cur["X"]
         Uo, Us = torch.empty_like(cur["U"]), torch.empty_like(cur["U"])
         ex_u.halo_fill(lambda: interp_call(Uo, Xb), local=not fused_fill)
@@ -1085,67 +1151,91 @@ def main():
         elapsed = float(t.item())
     ctx.synchronize()
 
-    # per-kernel breakdown on the context stream (separate instrumented steps)
-    for _ in range(max(3, min(args.steps, 10))):
-        step(True)
-        collect()
-    # the sweep kernels alone: HIP events the library records around each
-    # launch on the context stream (ibtk_le_ctx_last_kernel_ms)
-    ctx.enable_timing(True)
-    kt = {"interp": [], "spread": []}
-    for _ in range(3):
-        ex_u.halo_fill(local=not fused_fill)
-        interp_call(cur["U"], cur["X"])
-        ctx.synchronize()
-        kt["interp"].append(ctx.last_kernel_ms())
-        zero_step()
-        spread_call(cur["F"], cur["X"])
-        ctx.synchronize()
-        kt["spread"].append(ctx.last_kernel_ms())
-    ctx.enable_timing(False)
-
     ms_per_step = 1e3 * elapsed / args.steps
     value = 2.0 * M_total * args.steps / elapsed
-    lds = lds_atomic(ctx, lambda: le.spread(ctx, bins, kernel, "side", geom, f, cur["F"], cur["X"]),
-                     sum(kt["spread"]) / len(kt["spread"]))
 
     def mean(v):
         return sum(v) / len(v)
 
-    t_i, t_s = mean(acc["interp"]), mean(acc["spread"])
-    k_i, k_s = mean(kt["interp"]), mean(kt["spread"])
-    B_i = M_local * 48 + 8 * sum(S_touched)
-    # the spread reads and writes the touched points; into a zeroed f (the default) it
-    # writes every point of f once and reads none
-    B_s = M_local * 48 + (8 * sum(a.numel() for a in f) if args.spread_into == "zero" else 16 * sum(S_touched))
-    dominant = "spread" if k_s >= k_i else "interp"
-    achieved = (B_s / (k_s * 1e-3) if dominant == "spread" else B_i / (k_i * 1e-3)) / 1e9
-    pair = (B_i + B_s) / ((t_i + t_s) * 1e-3) / 1e9
-    # HBM traffic per launch of the dominant kernel from the rocprofv3 PMC passes of
-    # tools/pmc_traffic.sh (2 x FETCH_SIZE + WRITE_SIZE: FETCH_SIZE counts half the
-    # bytes of 8- and 16-byte-per-lane reads on gfx950, profiles/r02b/
-    # fetch_calibration.json), used only if it profiled this very build
-    traffic, traffic_note = None, "no PMC profile of this build"
-    pmc = ROOT / "profiles" / f"pmc_{args.config}_{kernel}_{world}gpu.json"
-    if pmc.exists():
-        try:
-            from ibamr_amd.build import source_hash
-            rec = json.loads(pmc.read_text())
-            if rec.get("build") == source_hash():
-                traffic = rec.get("per_launch_bytes", {}).get(dominant)
-                traffic_note = (f"PMC {pmc.relative_to(ROOT)}: 2 x FETCH_SIZE + WRITE_SIZE per launch, "
-                                f"build {rec['build']}")
-            else:
-                traffic_note = f"PMC {pmc.relative_to(ROOT)} profiled build {rec.get('build')}, not this one"
-        except Exception as e:
-            traffic_note = f"PMC record unreadable: {e!r}"
+    if args.dump_outputs:
+        # what the last timed step handed back: U = J u at this rank's markers, f = S F on its
+        # slab (ghost planes included) and, moving, the updated positions
+        rows = int(n_dev.item()) if fixed else U.shape[0]
+        arrays = {"U": U[:rows], "f0": f[0], "f1": f[1], "f2": f[2]}
+        if args.move:
+            arrays["X"] = X[:rows]
+        dump_outputs(args.dump_outputs, arrays, f"_rank{rank}" if world > 1 else "", DUMP_SAMPLE // world)
 
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        try:
-            cpu = cpu_baseline(cfg, kernel, args.cpu_seconds)
-        except Exception as e:  # the baseline must never hide the GPU result
-            cpu = {"value": None, "error": repr(e)}
+    def full_record():
+        """--full: the instrumented steps, the sweep kernels alone, the roofline and LDS-atomic
+        records and the CPU baseline, after the timed steps."""
+        # per-kernel breakdown on the context stream (separate instrumented steps)
+        for _ in range(max(3, min(args.steps, 10))):
+            step(True)
+            collect()
+        # the sweep kernels alone: HIP events the library records around each
+        # launch on the context stream (ibtk_le_ctx_last_kernel_ms)
+        ctx.enable_timing(True)
+        kt = {"interp": [], "spread": []}
+        for _ in range(3):
+            ex_u.halo_fill(local=not fused_fill)
+            interp_call(cur["U"], cur["X"])
+            ctx.synchronize()
+            kt["interp"].append(ctx.last_kernel_ms())
+            zero_step()
+            spread_call(cur["F"], cur["X"])
+            ctx.synchronize()
+            kt["spread"].append(ctx.last_kernel_ms())
+        ctx.enable_timing(False)
+
+        lds = lds_atomic(ctx, lambda: le.spread(ctx, bins, kernel, "side", geom, f, cur["F"], cur["X"]),
+                         sum(kt["spread"]) / len(kt["spread"]))
+
+        t_i, t_s = mean(acc["interp"]), mean(acc["spread"])
+        k_i, k_s = mean(kt["interp"]), mean(kt["spread"])
+        B_i = M_local * 48 + 8 * sum(S_touched)
+        # the spread reads and writes the touched points; into a zeroed f (the default) it
+        # writes every point of f once and reads none
+        B_s = M_local * 48 + (8 * sum(a.numel() for a in f) if args.spread_into == "zero" else 16 * sum(S_touched))
+        dominant = "spread" if k_s >= k_i else "interp"
+        achieved = (B_s / (k_s * 1e-3) if dominant == "spread" else B_i / (k_i * 1e-3)) / 1e9
+        pair = (B_i + B_s) / ((t_i + t_s) * 1e-3) / 1e9
+        # HBM traffic per launch of the dominant kernel from the rocprofv3 PMC passes of
+        # tools/pmc_traffic.sh (2 x FETCH_SIZE + WRITE_SIZE: FETCH_SIZE counts half the
+        # bytes of 8- and 16-byte-per-lane reads on gfx950, profiles/r02b/
+        # fetch_calibration.json), used only if it profiled this very build
+        traffic, traffic_note = None, "no PMC profile of this build"
+        pmc = ROOT / "profiles" / f"pmc_{args.config}_{kernel}_{world}gpu.json"
+        if pmc.exists():
+            try:
+                from ibamr_amd.build import source_hash
+                rec = json.loads(pmc.read_text())
+                if rec.get("build") == source_hash():
+                    traffic = rec.get("per_launch_bytes", {}).get(dominant)
+                    traffic_note = (f"PMC {pmc.relative_to(ROOT)}: 2 x FETCH_SIZE + WRITE_SIZE per launch, "
+                                    f"build {rec['build']}")
+                else:
+                    traffic_note = f"PMC {pmc.relative_to(ROOT)} profiled build {rec.get('build')}, not this one"
+            except Exception as e:
+                traffic_note = f"PMC record unreadable: {e!r}"
+
+        cpu = None
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            try:
+                cpu = cpu_baseline(cfg, kernel, args.cpu_seconds)
+            except Exception as e:  # the baseline must never hide the GPU result
+                cpu = {"value": None, "error": repr(e)}
+
+        roofline = {"bound": "hbm", "kernel": dominant, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_unit": "bytes per launch (PMC)",
+                    "traffic_note": traffic_note,
+                    "algorithmic_bytes": {"interp": B_i, "spread": B_s},
+                    "kernel_ms": {"interp": k_i, "spread": k_s},
+                    "kernel_note": KERNEL_NOTE,
+                    "pair_achieved": pair, "pair_frac": pair / HBM_PEAK_GBS, "lds_atomic": lds}
+        return roofline, cpu, {k: mean(v) for k, v in acc.items()}
+
+    roofline, cpu, breakdown = full_record() if args.full else (None, None, None)
 
     zname = "zero f" if args.spread_into == "zero" else "zero ghosts"
     out = {
@@ -1188,14 +1278,11 @@ def main():
                              "; the ghost zeroing fused into the spread sweep (ibtk_le_zero_ghosts_spread)")) +
                            ("" if args.unfused_fill else
                             "; the periodic ghost fill fused into the interp sweep (ibtk_le_fill_interp)")},
-        "roofline": {"bound": "hbm", "kernel": dominant, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_unit": "bytes per launch (PMC)", "traffic_note": traffic_note,
-                     "algorithmic_bytes": {"interp": B_i, "spread": B_s},
-                     "kernel_ms": {"interp": k_i, "spread": k_s},
-                     "kernel_note": KERNEL_NOTE,
-                     "pair_achieved": pair, "pair_frac": pair / HBM_PEAK_GBS, "lds_atomic": lds},
+        # --full only: the roofline, the CPU baseline, the per-phase breakdown, the touched points
+        "full": args.full,
+        "roofline": roofline,
         "cpu_baseline": cpu,
-        "breakdown_ms": {k: mean(v) for k, v in acc.items()},
+        "breakdown_ms": breakdown,
         "touched_points": S_touched,
     }
     if args.solo_slab > 1:  # a projection aid, never the metric

@@ -94,7 +94,7 @@ def test_bench_gpus2_rehearsal_launches_two_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(IBTK_BENCH_BACKEND="gloo", IBTK_BENCH_DEVICE="0")
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--config", "cfg2",
-                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+                        "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-3000:]
     # (gloo itself prints a connection note on stdout; the record is the one JSON line)

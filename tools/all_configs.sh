@@ -6,7 +6,7 @@ out=gpurun_out/$1; mkdir -p $out
 export TMPDIR=/tmp
 run() {  # name, bench args...
   local name=$1; shift
-  timeout -k 10 300 python -u bench.py --steps 5 --warmup 2 --no-cpu-baseline "$@" > $out/$name.json 2> $out/$name.err \
+  timeout -k 10 300 python -u bench.py --steps 5 --warmup 2 --full --no-cpu-baseline "$@" > $out/$name.json 2> $out/$name.err \
     || { echo "$name failed"; tail -5 $out/$name.err; exit 1; }
   python3 -c "import json;d=json.load(open('$out/$name.json'));print('$name', '%.3e'%d['value'], 'frac %.3f'%d['roofline']['frac'], d['breakdown_ms'])"
 }

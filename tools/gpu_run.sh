@@ -14,7 +14,7 @@ for job in "$@"; do
       [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc ;;
     bench:*)
       IFS=: read -r _ cfg steps <<< "$job"; steps=${steps:-5}
-      timeout -k 10 400 python -u bench.py --config $cfg --steps $steps --warmup 2 --no-cpu-baseline > $out/bench_$cfg.json 2> $out/bench_$cfg.err
+      timeout -k 10 400 python -u bench.py --config $cfg --steps $steps --warmup 2 --full --no-cpu-baseline > $out/bench_$cfg.json 2> $out/bench_$cfg.err
       rc=$?; echo "bench $cfg rc=$rc"; [ $rc -eq 0 ] || { tail -5 $out/bench_$cfg.err; exit $rc; }
       python3 -c "import json;d=json.load(open('$out/bench_$cfg.json'));print('$cfg', '%.3e'%d['value'], d['breakdown_ms'], 'frac %.3f'%d['roofline']['frac'])" ;;
     prof:*)

@@ -9,6 +9,6 @@ out=gpurun_out/$1; n=$2; shift 2
 mkdir -p $out
 export TMPDIR=/tmp IBTK_BENCH_BACKEND=gloo IBTK_BENCH_DEVICE=0
 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 \
-  --master-port $((29500 + n)) bench.py --gpus $n --no-cpu-baseline "$@" > $out/rehearse_$n.json 2> $out/rehearse_$n.err \
+  --master-port $((29500 + n)) bench.py --gpus $n --full --no-cpu-baseline "$@" > $out/rehearse_$n.json 2> $out/rehearse_$n.err \
   || { echo "rehearsal N=$n failed"; tail -20 $out/rehearse_$n.err; exit 1; }
 cat $out/rehearse_$n.json

@@ -8,7 +8,7 @@ i=0
 for a in "$@"; do
   i=$((i+1))
   BENCH_ARGS="$a" bash tools/pmc_traffic.sh $out/pmc$i cfg4 IB_4 > $out/pmc$i.log 2>&1 || { echo "pmc $i failed"; tail -3 $out/pmc$i.log; exit 1; }
-  timeout -k 10 300 python -u bench.py --steps 10 --warmup 2 --no-cpu-baseline $a > $out/b$i.json 2> $out/b$i.err || { echo "bench $i failed"; exit 1; }
+  timeout -k 10 300 python -u bench.py --steps 10 --warmup 2 --full --no-cpu-baseline $a > $out/b$i.json 2> $out/b$i.err || { echo "bench $i failed"; exit 1; }
   python3 -c "
 import json
 p=json.load(open('$out/pmc$i/pmc.json')); d=json.load(open('$out/b$i.json'))
