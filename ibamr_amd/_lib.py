@@ -123,6 +123,12 @@ _SIGS = [
       c_int]),
     ("ibtk_le_position_update", c_int,
      [c_void_p, c_int, ctypes.c_longlong, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("ibtk_le_forcegen_create", c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_void_p)]),
+    ("ibtk_le_forcegen_destroy", c_int, [c_void_p]),
+    ("ibtk_le_forcegen_set_springs", c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("ibtk_le_forcegen_set_beams", c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("ibtk_le_forcegen_set_targets", c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("ibtk_le_forcegen_compute", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     ("ibtk_le_slab_update_partition", c_int,
      [c_void_p, c_int, ctypes.c_longlong, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
       c_int, c_void_p, c_void_p]),

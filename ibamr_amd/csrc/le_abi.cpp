@@ -3087,3 +3087,222 @@ extern "C" int ibtk_le_mark_stencils(ibtk_le_ctx ctx, ibtk_le_markers m, int ker
     HIP_TRY(launch_mark(geom->ndim, kernel, p, m->n, mk, ctx->stream));
     return IBTK_LE_OK;
 }
+
+// ---------------------------------------------------------------------------
+// Lagrangian force generation: springs, beams, target points (IBStandardForceGen).
+// The set_* calls build the per-node incidence lists on the host (a stable counting
+// sort, so every node's entries stay in ascending k) and upload them; compute is one
+// launch of le_force.hip's gather kernel on the context stream.
+// ---------------------------------------------------------------------------
+struct ibtk_le_forcegen_s {
+    ibtk_le_ctx ctx = nullptr;
+    int ndim = 0, n = 0;
+    DevBuf soff, srec, boff, brec, toff, trec;
+    long long ns = 0, nb = 0, nt = 0;  // springs, beams, target points in the plan
+    bool need_U = false;               // some target point has eta != 0
+};
+
+extern "C" int ibtk_le_forcegen_create(ibtk_le_ctx ctx, int ndim, int n_nodes, ibtk_le_forcegen* out) {
+    if (!ctx) return fail(IBTK_LE_ERR_ARG, "forcegen_create: null context");
+    if (!out) return fail(IBTK_LE_ERR_ARG, "forcegen_create: null out");
+    if (ndim != 2 && ndim != 3) return fail(IBTK_LE_ERR_ARG, "forcegen_create: ndim %d is not 2 or 3", ndim);
+    if (n_nodes < 0) return fail(IBTK_LE_ERR_ARG, "forcegen_create: negative node count %d", n_nodes);
+    auto* fg = new ibtk_le_forcegen_s();
+    fg->ctx = ctx;
+    fg->ndim = ndim;
+    fg->n = n_nodes;
+    *out = fg;
+    return IBTK_LE_OK;
+}
+
+extern "C" int ibtk_le_forcegen_destroy(ibtk_le_forcegen fg) {
+    if (!fg) return IBTK_LE_OK;
+    hipSetDevice(fg->ctx->device);
+    hipStreamSynchronize(fg->ctx->stream);
+    for (DevBuf* b : {&fg->soff, &fg->srec, &fg->boff, &fg->brec, &fg->toff, &fg->trec}) b->release();
+    delete fg;
+    return IBTK_LE_OK;
+}
+
+namespace {
+// Row offsets of the incidence lists: cnt[i] entries at node i.  64-bit, so no plan an
+// int count of springs / beams can describe overflows them.
+std::vector<long long> fg_offsets(const std::vector<int>& cnt) {
+    std::vector<long long> off(cnt.size() + 1, 0);
+    for (size_t i = 0; i < cnt.size(); ++i) off[i + 1] = off[i] + cnt[i];
+    return off;
+}
+
+// Replaces one class of the plan on the device (a blocking upload: the plan is built at
+// initialisation / regrid time, not in the step).
+int fg_upload(ibtk_le_forcegen fg, DevBuf& doff, DevBuf& drec, const std::vector<long long>& off, const void* rec,
+              size_t rec_bytes) {
+    HIP_TRY(hipSetDevice(fg->ctx->device));
+    HIP_TRY(hipStreamSynchronize(fg->ctx->stream));  // an earlier compute may still read the old plan
+    if (int rc = doff.ensure(off.size() * sizeof(long long))) return rc;
+    if (int rc = drec.ensure(std::max<size_t>(rec_bytes, 8))) return rc;
+    HIP_TRY(hipMemcpy(doff.p, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice));
+    if (rec_bytes) HIP_TRY(hipMemcpy(drec.p, rec, rec_bytes, hipMemcpyHostToDevice));
+    return IBTK_LE_OK;
+}
+
+int fg_node(ibtk_le_forcegen fg, const char* what, const char* role, int k, int idx) {
+    if (idx < 0 || idx >= fg->n)
+        return fail(IBTK_LE_ERR_ARG, "%s %d: %s node index %d is out of range [0, %d)", what, k, role, idx, fg->n);
+    return IBTK_LE_OK;
+}
+
+template <int ND>
+int fg_set_beams(ibtk_le_forcegen fg, int n, const int* mastr, const int* next, const int* prev, const double* bend,
+                 const double* curv) {
+    std::vector<int> cnt(fg->n, 0);
+    for (int k = 0; k < n; ++k) {
+        ++cnt[mastr[k]];
+        ++cnt[next[k]];
+        ++cnt[prev[k]];
+    }
+    const std::vector<long long> off = fg_offsets(cnt);
+    std::vector<long long> pos(off.begin(), off.end() - 1);
+    std::vector<FgBeam<ND>> rec((size_t)off.back());
+    for (int k = 0; k < n; ++k) {
+        FgBeam<ND> r;
+        r.m = mastr[k];
+        r.nx = next[k];
+        r.pv = prev[k];
+        r.bend = bend[k];
+        for (int d = 0; d < ND; ++d) r.curv[d] = curv ? curv[(size_t)k * ND + d] : 0.0;
+        const int nodes[3] = {r.m, r.nx, r.pv};  // the reference's statement order within one k
+        for (int role = 0; role < 3; ++role) {
+            r.role = role;
+            rec[(size_t)pos[nodes[role]]++] = r;
+        }
+    }
+    return fg_upload(fg, fg->boff, fg->brec, off, rec.data(), rec.size() * sizeof(FgBeam<ND>));
+}
+
+template <int ND>
+int fg_set_targets(ibtk_le_forcegen fg, int n, const int* node, const double* kappa, const double* eta,
+                   const double* X0) {
+    std::vector<int> cnt(fg->n, 0);
+    for (int k = 0; k < n; ++k) ++cnt[node[k]];
+    const std::vector<long long> off = fg_offsets(cnt);
+    std::vector<long long> pos(off.begin(), off.end() - 1);
+    std::vector<FgTarget<ND>> rec((size_t)off.back());
+    for (int k = 0; k < n; ++k) {
+        FgTarget<ND> r;
+        r.kappa = kappa[k];
+        r.eta = eta ? eta[k] : 0.0;
+        for (int d = 0; d < ND; ++d) r.X0[d] = X0[(size_t)k * ND + d];
+        rec[(size_t)pos[node[k]]++] = r;
+    }
+    return fg_upload(fg, fg->toff, fg->trec, off, rec.data(), rec.size() * sizeof(FgTarget<ND>));
+}
+}  // namespace
+
+extern "C" int ibtk_le_forcegen_set_springs(ibtk_le_forcegen fg, int n, const int* mastr, const int* slave,
+                                            const double* kappa, const double* rest, const int* fcn_idx) {
+    if (!fg) return fail(IBTK_LE_ERR_ARG, "forcegen_set_springs: null force generator");
+    if (n < 0) return fail(IBTK_LE_ERR_ARG, "forcegen_set_springs: negative spring count %d", n);
+    if (n > 0 && (!mastr || !slave || !kappa || !rest)) return fail(IBTK_LE_ERR_ARG, "forcegen_set_springs: null array");
+    for (int k = 0; k < n; ++k) {
+        if (int rc = fg_node(fg, "spring", "master", k, mastr[k])) return rc;
+        if (int rc = fg_node(fg, "spring", "slave", k, slave[k])) return rc;
+        if (mastr[k] == slave[k])
+            return fail(IBTK_LE_ERR_ARG, "spring %d: master and slave are both node %d", k, mastr[k]);
+        if (fcn_idx && fcn_idx[k] != 0)
+            return fail(IBTK_LE_ERR_ARG,
+                        "spring %d: force function index %d: only the default Hookean law (index 0) runs on the "
+                        "device; registered host spring force functions are not supported",
+                        k, fcn_idx[k]);
+    }
+    fg->ns = 0;
+    if (n == 0) return IBTK_LE_OK;
+    std::vector<int> cnt(fg->n, 0);
+    for (int k = 0; k < n; ++k) {
+        ++cnt[mastr[k]];
+        ++cnt[slave[k]];
+    }
+    const std::vector<long long> off = fg_offsets(cnt);
+    std::vector<long long> pos(off.begin(), off.end() - 1);
+    std::vector<FgSpring> rec((size_t)off.back());
+    for (int k = 0; k < n; ++k) {
+        const FgSpring r{mastr[k], slave[k], kappa[k], rest[k]};
+        rec[(size_t)pos[r.m]++] = r;
+        rec[(size_t)pos[r.s]++] = r;
+    }
+    if (int rc = fg_upload(fg, fg->soff, fg->srec, off, rec.data(), rec.size() * sizeof(FgSpring))) return rc;
+    fg->ns = n;
+    return IBTK_LE_OK;
+}
+
+extern "C" int ibtk_le_forcegen_set_beams(ibtk_le_forcegen fg, int n, const int* mastr, const int* next,
+                                          const int* prev, const double* bend, const double* curv) {
+    if (!fg) return fail(IBTK_LE_ERR_ARG, "forcegen_set_beams: null force generator");
+    if (n < 0) return fail(IBTK_LE_ERR_ARG, "forcegen_set_beams: negative beam count %d", n);
+    if (n > 0 && (!mastr || !next || !prev || !bend)) return fail(IBTK_LE_ERR_ARG, "forcegen_set_beams: null array");
+    for (int k = 0; k < n; ++k) {
+        if (int rc = fg_node(fg, "beam", "master", k, mastr[k])) return rc;
+        if (int rc = fg_node(fg, "beam", "next", k, next[k])) return rc;
+        if (int rc = fg_node(fg, "beam", "prev", k, prev[k])) return rc;
+        if (mastr[k] == next[k]) return fail(IBTK_LE_ERR_ARG, "beam %d: master and next are both node %d", k, mastr[k]);
+        if (mastr[k] == prev[k]) return fail(IBTK_LE_ERR_ARG, "beam %d: master and prev are both node %d", k, mastr[k]);
+    }
+    fg->nb = 0;
+    if (n == 0) return IBTK_LE_OK;
+    const int rc = fg->ndim == 2 ? fg_set_beams<2>(fg, n, mastr, next, prev, bend, curv)
+                                 : fg_set_beams<3>(fg, n, mastr, next, prev, bend, curv);
+    if (rc) return rc;
+    fg->nb = n;
+    return IBTK_LE_OK;
+}
+
+extern "C" int ibtk_le_forcegen_set_targets(ibtk_le_forcegen fg, int n, const int* node, const double* kappa,
+                                            const double* eta, const double* X0) {
+    if (!fg) return fail(IBTK_LE_ERR_ARG, "forcegen_set_targets: null force generator");
+    if (n < 0) return fail(IBTK_LE_ERR_ARG, "forcegen_set_targets: negative target point count %d", n);
+    if (n > 0 && (!node || !kappa || !X0)) return fail(IBTK_LE_ERR_ARG, "forcegen_set_targets: null array");
+    for (int k = 0; k < n; ++k)
+        if (int rc = fg_node(fg, "target point", "its", k, node[k])) return rc;
+    fg->nt = 0;
+    fg->need_U = false;
+    if (n == 0) return IBTK_LE_OK;
+    const int rc = fg->ndim == 2 ? fg_set_targets<2>(fg, n, node, kappa, eta, X0)
+                                 : fg_set_targets<3>(fg, n, node, kappa, eta, X0);
+    if (rc) return rc;
+    fg->nt = n;
+    for (int k = 0; eta && k < n; ++k) fg->need_U = fg->need_U || eta[k] != 0.0;
+    return IBTK_LE_OK;
+}
+
+extern "C" int ibtk_le_forcegen_compute(ibtk_le_ctx ctx, ibtk_le_forcegen fg, const double* X_dev,
+                                        const double* dX_dev, const double* U_dev, double* F_dev, int accumulate) {
+    if (!ctx) return fail(IBTK_LE_ERR_ARG, "forcegen_compute: null context");
+    if (!fg) return fail(IBTK_LE_ERR_ARG, "forcegen_compute: null force generator");
+    if (ctx->device != fg->ctx->device)
+        return fail(IBTK_LE_ERR_ARG, "forcegen_compute: the plan lives on device %d, the context on %d", fg->ctx->device,
+                    ctx->device);
+    if (fg->n == 0) return IBTK_LE_OK;
+    if (!X_dev || !F_dev) return fail(IBTK_LE_ERR_ARG, "forcegen_compute: null array");
+    if (fg->need_U && !U_dev)
+        return fail(IBTK_LE_ERR_ARG, "forcegen_compute: a target point has a damping coefficient eta != 0, U is needed");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (fg->ns == 0 && fg->nb == 0 && fg->nt == 0) {
+        if (!accumulate) HIP_TRY(hipMemsetAsync(F_dev, 0, sizeof(double) * (size_t)fg->n * fg->ndim, ctx->stream));
+        return IBTK_LE_OK;
+    }
+    ForceGenParams p{};
+    p.n = fg->n;
+    p.soff = fg->ns ? fg->soff.as<long long>() : nullptr;
+    p.boff = fg->nb ? fg->boff.as<long long>() : nullptr;
+    p.toff = fg->nt ? fg->toff.as<long long>() : nullptr;
+    p.srec = fg->srec.as<FgSpring>();
+    p.brec = fg->brec.p;
+    p.trec = fg->trec.p;
+    p.X = X_dev;
+    p.dX = dX_dev;
+    p.U = U_dev;
+    p.F = F_dev;
+    p.accumulate = accumulate ? 1 : 0;
+    HIP_TRY(launch_forcegen(fg->ndim, p, ctx->stream));
+    return IBTK_LE_OK;
+}

@@ -294,6 +294,35 @@ hipError_t launch_slab_update_partition(int scheme, long M, double dt, const dou
                                         int* counts, hipStream_t s);
 hipError_t launch_position_update(int scheme, long n, double dt, const double* X, const double* U0, const double* U1,
                                   double* Xn, hipStream_t s);
+
+// The force plan of ibtk_le_forcegen (le_force.hip): per node, a CSR row of spring
+// entries (ascending spring number k), one of beam entries (ascending k; within one k
+// the roles master 0, next 1, prev 2) and one of target-point entries.  Every entry
+// holds the whole record of its spring / beam, node indices in [0, n).
+struct FgSpring {
+    int m, s;  // master, slave: D = X[s] - X[m] at both ends
+    double kappa, rest;
+};
+template <int ND>
+struct FgBeam {
+    int m, nx, pv, role;
+    double bend, curv[ND];
+};
+template <int ND>
+struct FgTarget {
+    double kappa, eta, X0[ND];
+};
+struct ForceGenParams {
+    long n;                                // nodes
+    const long long *soff, *boff, *toff;   // n + 1 row offsets each; NULL: no such entries
+    const FgSpring* srec;
+    const void* brec;                      // FgBeam<ndim>
+    const void* trec;                      // FgTarget<ndim>
+    const double *X, *dX, *U;              // dX, U may be NULL
+    double* F;
+    int accumulate;                        // F = F + acc, else F = acc
+};
+hipError_t launch_forcegen(int ndim, const ForceGenParams& p, hipStream_t s);
 hipError_t launch_gather_col(int kernel, const Params& p, int n, int* sorted_s, double* sorted_X,
                              const unsigned* sorted_key, int nbuckets, int* bucket_start, hipStream_t s);
 hipError_t launch_interp_sweep(int kernel, const Params& p, int n, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);

@@ -1,0 +1,286 @@
+"""Lagrangian force generation on the device: springs, beams and target points.
+
+``IBStandardForceGen::computeLagrangianForce`` (``src/IB/IBStandardForceGen.cpp:265-313``)
+produces the ``F`` that ``spread`` consumes, from ``X`` and ``U``, every step between the
+position update and the spread.  Two pieces live here:
+
+* :class:`ForceSpecs` -- the host side.  It holds what the deck readers of
+  :mod:`ibamr_amd.io` return for one or more structures and flattens it into the arrays
+  ``IBStandardForceGen::initialize{Spring,Beam,TargetPoint}LevelData`` cache
+  (``:700-776``, ``:894-988``, ``:1101-1148``), in the reference's order: master by master
+  in local node order, deck order within a master
+  (``IBStandardInitializer::initializeSpecs``, ``IBStandardInitializer.cpp:2815-2952``).
+
+* :class:`ForceGen` -- the device plan built through the C ABI
+  (``ibtk_le_forcegen_*``) and its ``compute``: one gather kernel, a lane per node,
+  the serial loops' result bit for bit, no host synchronisation.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+import sys
+from typing import NamedTuple, Optional, Sequence
+
+import numpy as np
+
+from . import _lib, io
+from ._lib import check
+
+__all__ = ["SpringArrays", "BeamArrays", "TargetArrays", "ForceSpecs", "ForceGen"]
+
+
+class SpringArrays(NamedTuple):
+    mastr: np.ndarray    # (n,) int32 node index of the master
+    slave: np.ndarray    # (n,) int32
+    kappa: np.ndarray    # (n,) float64
+    rest: np.ndarray     # (n,) float64
+    fcn_idx: np.ndarray  # (n,) int32; only 0, the default Hookean law, runs on the device
+
+
+class BeamArrays(NamedTuple):
+    mastr: np.ndarray  # (n,) int32
+    next: np.ndarray   # (n,) int32
+    prev: np.ndarray   # (n,) int32
+    bend: np.ndarray   # (n,) float64
+    curv: np.ndarray   # (n, ndim) float64
+
+
+class TargetArrays(NamedTuple):
+    node: np.ndarray   # (n,) int32
+    kappa: np.ndarray  # (n,) float64
+    eta: np.ndarray    # (n,) float64
+    X0: np.ndarray     # (n, ndim) float64 the vertex's initial position
+
+
+def _i32(a, n=None):
+    a = np.ascontiguousarray(np.asarray(a).reshape(-1), dtype=np.int32)
+    if n is not None and a.size != n:
+        raise ValueError(f"expected {n} entries, got {a.size}")
+    return a
+
+
+def _f64(a, shape):
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(shape))
+    return a
+
+
+class ForceSpecs:
+    """The force specifications of one or more structures, in Lagrangian vertex indices.
+
+    ``X0`` is the ``(num_vertex, ndim)`` array of initial vertex positions (the target
+    points' anchors); ``springs`` / ``beams`` / ``targets`` are an ``io.SpringDeck`` /
+    ``io.BeamDeck`` / ``io.TargetDeck`` (or None) whose indices already include the
+    structure's vertex offset.  Several structures are joined with :meth:`concat`.
+    """
+
+    def __init__(self, ndim: int, X0: np.ndarray, springs: Optional[io.SpringDeck] = None,
+                 beams: Optional[io.BeamDeck] = None, targets: Optional[io.TargetDeck] = None):
+        if ndim not in (2, 3):
+            raise ValueError("ndim must be 2 or 3")
+        self.ndim = ndim
+        self.X0 = _f64(X0, (-1, ndim))
+        self.springs = springs
+        self.beams = beams
+        self.targets = targets
+
+    @property
+    def num_vertex(self) -> int:
+        return self.X0.shape[0]
+
+    @classmethod
+    def from_files(cls, base: str | os.PathLike, ndim: int, vertex_offset: int = 0, length_scale: float = 1.0,
+                   posn_shift: Optional[Sequence[float]] = None, uniform_stiffness: Optional[float] = None,
+                   uniform_rest_length: Optional[float] = None, uniform_force_fcn_idx: Optional[int] = None,
+                   uniform_bend_rigidity: Optional[float] = None,
+                   uniform_curvature: Optional[Sequence[float]] = None,
+                   uniform_target_stiffness: Optional[float] = None,
+                   uniform_target_damping: Optional[float] = None) -> "ForceSpecs":
+        """Read ``base.vertex`` and whichever of ``base.spring``, ``base.beam`` and
+        ``base.target`` exist.  ``vertex_offset`` is the structure's first Lagrangian index
+        (the vertex counts of the structures before it)."""
+        base = os.fspath(base)
+        X0 = io.read_vertex(base + ".vertex", ndim, length_scale, posn_shift)
+        nv = X0.shape[0]
+        springs = beams = targets = None
+        if os.path.isfile(base + ".spring"):
+            springs = io.read_spring(base + ".spring", nv, vertex_offset, length_scale, uniform_stiffness,
+                                     uniform_rest_length, uniform_force_fcn_idx)
+        if os.path.isfile(base + ".beam"):
+            beams = io.read_beam(base + ".beam", nv, ndim, vertex_offset, uniform_bend_rigidity, uniform_curvature)
+        if os.path.isfile(base + ".target"):
+            targets = io.read_target(base + ".target", nv, vertex_offset, uniform_target_stiffness,
+                                     uniform_target_damping)
+        if vertex_offset:
+            # X0 is indexed by Lagrangian index: rows below the offset belong to other structures
+            X0 = np.concatenate([np.full((vertex_offset, ndim), np.nan), X0])
+        return cls(ndim, X0, springs, beams, targets)
+
+    @classmethod
+    def concat(cls, parts: Sequence["ForceSpecs"]) -> "ForceSpecs":
+        """Join structures read with consecutive vertex offsets (part j's offset = the rows
+        of the parts before it)."""
+        if not parts:
+            raise ValueError("no structures")
+        ndim = parts[0].ndim
+        X0 = np.empty((0, ndim))
+        for p in parts:
+            if p.ndim != ndim:
+                raise ValueError("structures of different ndim")
+            if p.X0.shape[0] < X0.shape[0] or not np.all(np.isnan(p.X0[:X0.shape[0]])):
+                raise ValueError("vertex offsets do not follow the structures' vertex counts")
+            X0 = np.concatenate([X0, p.X0[X0.shape[0]:]])
+
+        def join(decks, typ):
+            decks = [d for d in decks if d is not None]
+            if not decks:
+                return None
+            cols = []
+            for f in typ._fields:
+                vals = [getattr(d, f) for d in decks]
+                cols.append(sum(vals, []) if isinstance(vals[0], list) else np.concatenate(vals))
+            return typ(*cols)
+
+        return cls(ndim, X0, join([p.springs for p in parts], io.SpringDeck),
+                   join([p.beams for p in parts], io.BeamDeck), join([p.targets for p in parts], io.TargetDeck))
+
+    def arrays(self, perm: Optional[np.ndarray] = None) -> dict:
+        """The flat arrays in the reference's order, as ``{"springs": SpringArrays | None,
+        "beams": BeamArrays | None, "targets": TargetArrays | None}``.
+
+        ``perm[lagrangian index] = local node index`` (None: the identity).  The order
+        ``le.node_distribution`` returns maps the other way (``order[i]`` = the input index of
+        node ``i``): its inverse fits here.
+
+        * An edge has its smaller Lagrangian index first: that vertex is the master
+          (``IBStandardInitializer.cpp:979-982``).
+        * Springs and beams are sorted stably by the master's local index, so deck order
+          survives within a master (the multimaps of ``:983``, ``:1401`` walked at ``:2828``,
+          ``:2894``).
+        * A repeated edge yields one spring per line, every one with the parameters of the
+          edge's first line: the edge multimap keeps each entry, the spec map's ``insert``
+          only the first (``:983-987``, ``:2848``).
+        * Target points are ordered by local node index.
+        """
+        nv = self.num_vertex
+        if perm is None:
+            perm = np.arange(nv, dtype=np.int64)
+        else:
+            perm = np.asarray(perm, dtype=np.int64).reshape(-1)
+            if perm.size != nv:
+                raise ValueError(f"perm has {perm.size} entries, the structures {nv} vertices")
+        out = {"springs": None, "beams": None, "targets": None}
+        if self.springs is not None:
+            s = self.springs
+            m = np.minimum(s.mastr, s.slave).astype(np.int64)
+            v = np.maximum(s.mastr, s.slave).astype(np.int64)
+            first: dict = {}
+            src = np.empty(m.size, dtype=np.int64)
+            for k, e in enumerate(zip(m.tolist(), v.tolist())):
+                src[k] = first.setdefault(e, k)
+            o = np.argsort(perm[m], kind="stable")
+            out["springs"] = SpringArrays(_i32(perm[m][o]), _i32(perm[v][o]), s.kappa[src][o].copy(),
+                                          s.rest[src][o].copy(), _i32(s.fcn_idx[src][o]))
+        if self.beams is not None:
+            b = self.beams
+            o = np.argsort(perm[b.mastr.astype(np.int64)], kind="stable")
+            out["beams"] = BeamArrays(_i32(perm[b.mastr][o]), _i32(perm[b.next][o]), _i32(perm[b.prev][o]),
+                                      b.bend[o].copy(), _f64(b.curv[o], (-1, self.ndim)))
+        if self.targets is not None:
+            t = self.targets
+            o = np.argsort(perm[t.node.astype(np.int64)], kind="stable")
+            out["targets"] = TargetArrays(_i32(perm[t.node][o]), t.kappa[o].copy(), t.eta[o].copy(),
+                                          _f64(self.X0[t.node[o]], (-1, self.ndim)))
+        return out
+
+
+def _host_ptr(a: Optional[np.ndarray]):
+    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+class ForceGen:
+    """A device force plan over ``n_nodes`` nodes (``ibtk_le_forcegen``).
+
+    ``springs = (mastr, slave, kappa, rest[, fcn_idx])``, ``beams = (mastr, next, prev, bend,
+    curv)`` and ``targets = (node, kappa, eta, X0)`` are host arrays of node indices in
+    ``[0, n_nodes)`` -- :meth:`ForceSpecs.arrays` output fits; ``n_nodes`` may include
+    trailing ghost nodes.  The plan is built once (host counting sort, one upload);
+    :meth:`compute` then runs one kernel on the context stream.
+    """
+
+    def __init__(self, ctx, n_nodes: int, ndim: int, springs=None, beams=None, targets=None):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        self.n_nodes = int(n_nodes)
+        self.ndim = int(ndim)
+        h = ctypes.c_void_p()
+        check(self.lib.ibtk_le_forcegen_create(ctx.h, self.ndim, self.n_nodes, ctypes.byref(h)))
+        self.h = h
+        if springs is not None:
+            self.set_springs(*springs)
+        if beams is not None:
+            self.set_beams(*beams)
+        if targets is not None:
+            self.set_targets(*targets)
+
+    @classmethod
+    def from_specs(cls, ctx, specs: ForceSpecs, perm=None, n_nodes: Optional[int] = None) -> "ForceGen":
+        a = specs.arrays(perm)
+        return cls(ctx, specs.num_vertex if n_nodes is None else n_nodes, specs.ndim, a["springs"], a["beams"],
+                   a["targets"])
+
+    def set_springs(self, mastr, slave, kappa, rest, fcn_idx=None):
+        mastr = _i32(mastr)
+        n = mastr.size
+        slave, kappa, rest = _i32(slave, n), _f64(kappa, (n,)), _f64(rest, (n,))
+        fcn = None if fcn_idx is None else _i32(fcn_idx, n)
+        check(self.lib.ibtk_le_forcegen_set_springs(self.h, n, _host_ptr(mastr), _host_ptr(slave), _host_ptr(kappa),
+                                                    _host_ptr(rest), _host_ptr(fcn)))
+
+    def set_beams(self, mastr, next, prev, bend, curv=None):
+        mastr = _i32(mastr)
+        n = mastr.size
+        next, prev, bend = _i32(next, n), _i32(prev, n), _f64(bend, (n,))
+        curv = None if curv is None else _f64(curv, (n, self.ndim))
+        check(self.lib.ibtk_le_forcegen_set_beams(self.h, n, _host_ptr(mastr), _host_ptr(next), _host_ptr(prev),
+                                                  _host_ptr(bend), _host_ptr(curv)))
+
+    def set_targets(self, node, kappa, eta, X0):
+        node = _i32(node)
+        n = node.size
+        kappa, X0 = _f64(kappa, (n,)), _f64(X0, (n, self.ndim))
+        eta = None if eta is None else _f64(eta, (n,))
+        check(self.lib.ibtk_le_forcegen_set_targets(self.h, n, _host_ptr(node), _host_ptr(kappa), _host_ptr(eta),
+                                                    _host_ptr(X0)))
+
+    def compute(self, X, U=None, F=None, dX=None, accumulate: bool = True):
+        """``F += acc`` (``accumulate``) or ``F = acc``, with ``acc`` the spring, beam and
+        target-point forces at ``X + dX``; ``[n_nodes][ndim]`` float64 device tensors.
+        ``F=None`` allocates the result.  ``U`` may be None unless a target point has a
+        non-zero damping coefficient.  Returns ``F``.  No host synchronisation."""
+        import torch
+
+        from .le import _ptr
+        shape = (self.n_nodes, self.ndim)
+        if F is None:
+            F = torch.empty(shape, dtype=torch.float64, device=X.device)
+            accumulate = False
+        for name, t in (("X", X), ("U", U), ("F", F), ("dX", dX)):
+            if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != shape):
+                raise ValueError(f"{name} must be a float64 tensor of shape {shape}")
+        check(self.lib.ibtk_le_forcegen_compute(self.ctx.h, self.h, _ptr(X), _ptr(dX), _ptr(U), _ptr(F),
+                                                int(bool(accumulate))))
+        return F
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.lib.ibtk_le_forcegen_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        if sys.is_finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -1,6 +1,6 @@
 """Wire and disk formats at the edges of the LE path.
 
-Two formats let marker data move between this library and an IBAMR run:
+These formats let marker data move between this library and an IBAMR run:
 
 * ``.vertex`` files, the input-deck format of ``IBStandardInitializer``
   (reader: ``src/IB/IBStandardInitializer.cpp:725-790``; sample:
@@ -11,6 +11,13 @@ Two formats let marker data move between this library and an IBAMR run:
   ``istringstream >>`` ignores them.  The reader applies
   ``X = length_scale * (X + posn_shift)`` per coordinate (:776).  Errors follow the
   reference's messages: premature end of file, invalid entry, count <= 0.
+
+* ``.spring``, ``.beam`` and ``.target`` files, the force-specification decks that sit
+  beside a ``.vertex`` file (readers: ``IBStandardInitializer.cpp:803-1006``,
+  ``:1240-1405``, ``:1740-1870``; samples: ``examples/IB/explicit/ex3/fila_256.*``).
+  Line 1 holds the record count; each following line holds vertex indices and material
+  parameters.  ``ibamr_amd.forcegen.ForceSpecs`` turns them into the flat arrays
+  ``IBStandardForceGen`` caches.
 
 * The ``LNodeIndex`` stream record (``ibtk/include/ibtk/private/LNodeIndex-inl.h:148-172``):
   three ``int`` (Lagrangian index, global PETSc index, local PETSc index), then
@@ -32,12 +39,14 @@ columns travel as payload.
 from __future__ import annotations
 
 import os
-from typing import Iterable, Optional, Sequence, Tuple
+from typing import Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
 __all__ = [
     "read_vertex", "write_vertex",
+    "SpringDeck", "BeamDeck", "TargetDeck",
+    "read_spring", "write_spring", "read_beam", "write_beam", "read_target", "write_target",
     "lnode_index_dtype", "lnode_index_stream_size", "pack_lnode_indices", "unpack_lnode_indices",
     "pack_ltransaction", "unpack_ltransaction",
 ]
@@ -107,6 +116,251 @@ def write_vertex(path: str | os.PathLike, X: np.ndarray) -> None:
     with open(os.fspath(path), "w") as fh:
         fh.write(f"{X.shape[0]}\n")
         np.savetxt(fh, X, fmt="%.16e", delimiter=" ")
+
+
+class SpringDeck(NamedTuple):
+    """A ``.spring`` file in deck order; edges normalised so ``mastr < slave``."""
+    mastr: np.ndarray    # (n,) int32
+    slave: np.ndarray    # (n,) int32
+    kappa: np.ndarray    # (n,) float64 spring constant
+    rest: np.ndarray     # (n,) float64 resting length (times length_scale)
+    fcn_idx: np.ndarray  # (n,) int32 force function index (0: the default Hookean law)
+    extra: List[np.ndarray]  # per line, the parameters after the function index
+
+
+class BeamDeck(NamedTuple):
+    """A ``.beam`` file in deck order (the file's columns are prev, mastr, next)."""
+    mastr: np.ndarray  # (n,) int32, the "current" vertex
+    next: np.ndarray   # (n,) int32
+    prev: np.ndarray   # (n,) int32
+    bend: np.ndarray   # (n,) float64 bending rigidity
+    curv: np.ndarray   # (n, ndim) float64 mesh-dependent curvature
+
+
+class TargetDeck(NamedTuple):
+    """A ``.target`` file: one entry per vertex named, in order of first appearance."""
+    node: np.ndarray   # (n,) int32
+    kappa: np.ndarray  # (n,) float64 penalty spring constant
+    eta: np.ndarray    # (n,) float64 damping coefficient
+
+
+class _Deck:
+    """Line reader shared by the force-spec decks: the count line, then one record per
+    line, comments cut, errors in the reference's wording (IBStandardInitializer.cpp:
+    842-862, 871-926)."""
+
+    def __init__(self, path, what: str):
+        self.name = os.fspath(path)
+        if not os.path.isfile(self.name):
+            raise FileNotFoundError(f"Cannot find {what} file: {self.name}")
+        self.line = 0
+
+    def __enter__(self):
+        self.fh = open(self.name, "r")
+        return self
+
+    def __exit__(self, *exc):
+        self.fh.close()
+
+    def invalid(self, detail: str = ""):
+        msg = f"Invalid entry in input file encountered on line {self.line} of file {self.name}"
+        return ValueError(msg + (f"\n  {detail}" if detail else ""))
+
+    def tokens(self) -> List[str]:
+        self.line += 1
+        line = self.fh.readline()
+        if not line:
+            raise ValueError(f"Premature end to input file encountered before line {self.line} of file {self.name}")
+        return _discard_comments(line).split()
+
+    def count(self) -> int:
+        tok = self.tokens()
+        try:
+            n = int(tok[0])
+        except (IndexError, ValueError):
+            raise self.invalid() from None
+        if n <= 0:
+            raise self.invalid()
+        return n
+
+    def index(self, tok: List[str], col: int, num_vertex: int) -> int:
+        try:
+            i = int(tok[col])
+        except (IndexError, ValueError):
+            raise self.invalid() from None
+        if i < 0 or i >= num_vertex:
+            raise self.invalid(f"vertex index {i} is out of range")
+        return i
+
+    def value(self, tok: List[str], col: int, negative: str) -> float:
+        try:
+            v = float(tok[col])
+        except (IndexError, ValueError):
+            raise self.invalid() from None
+        if v < 0.0:
+            raise self.invalid(negative)
+        return v
+
+
+def read_spring(path: str | os.PathLike, num_vertex: int, vertex_offset: int = 0, length_scale: float = 1.0,
+                uniform_stiffness: Optional[float] = None, uniform_rest_length: Optional[float] = None,
+                uniform_force_fcn_idx: Optional[int] = None) -> SpringDeck:
+    """Read a ``.spring`` file: per line ``idx1 idx2 kappa rest [fcn_idx [params...]]``.
+
+    Follows IBStandardInitializer::readSpringFiles (IBStandardInitializer.cpp:803-1006):
+    indices are checked against ``[0, num_vertex)``, the rest length is scaled by
+    ``length_scale`` (:927), a missing function index is 0, further parameters are kept,
+    the uniform overrides replace the line's values (:943-954), ``vertex_offset`` is
+    added, and an edge is stored with its smaller index first (:979-982).
+    """
+    with _Deck(path, "spring") as deck:
+        n = deck.count()
+        mastr, slave = np.empty(n, np.int32), np.empty(n, np.int32)
+        kappa, rest, fcn = np.empty(n), np.empty(n), np.zeros(n, np.int32)
+        extra: List[np.ndarray] = []
+        for k in range(n):
+            tok = deck.tokens()
+            a = deck.index(tok, 0, num_vertex)
+            b = deck.index(tok, 1, num_vertex)
+            kappa[k] = deck.value(tok, 2, "spring constant is negative")
+            rest[k] = deck.value(tok, 3, "spring resting length is negative") * length_scale
+            more: List[float] = []
+            try:
+                fcn[k] = int(tok[4])
+                for t in tok[5:]:
+                    more.append(float(t))
+            except (IndexError, ValueError):
+                pass  # as the reference's stream extraction stops at the first token it cannot read
+            extra.append(np.asarray(more, dtype=np.float64))
+            if uniform_stiffness is not None:
+                kappa[k] = uniform_stiffness
+            if uniform_rest_length is not None:
+                rest[k] = uniform_rest_length
+            if uniform_force_fcn_idx is not None:
+                fcn[k] = uniform_force_fcn_idx
+            mastr[k], slave[k] = min(a, b) + vertex_offset, max(a, b) + vertex_offset
+    return SpringDeck(mastr, slave, kappa, rest, fcn, extra)
+
+
+def read_beam(path: str | os.PathLike, num_vertex: int, ndim: int = 3, vertex_offset: int = 0,
+              uniform_bend_rigidity: Optional[float] = None,
+              uniform_curvature: Optional[Sequence[float]] = None) -> BeamDeck:
+    """Read a ``.beam`` file: per line ``prev curr next bend [curv_0 .. curv_{ndim-1}]``.
+
+    Follows IBStandardInitializer::readBeamFiles (IBStandardInitializer.cpp:1240-1405): a
+    missing curvature is the zero vector, a partial one an error (:1339-1359).
+    """
+    if ndim not in (2, 3):
+        raise ValueError("ndim must be 2 or 3")
+    ucurv = None if uniform_curvature is None else np.asarray(uniform_curvature, dtype=np.float64)
+    if ucurv is not None and ucurv.shape != (ndim,):
+        raise ValueError("uniform_curvature must have ndim entries")
+    with _Deck(path, "beam") as deck:
+        n = deck.count()
+        mastr, nxt, prev = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.int32)
+        bend, curv = np.empty(n), np.zeros((n, ndim))
+        for k in range(n):
+            tok = deck.tokens()
+            prev[k] = deck.index(tok, 0, num_vertex) + vertex_offset
+            mastr[k] = deck.index(tok, 1, num_vertex) + vertex_offset
+            nxt[k] = deck.index(tok, 2, num_vertex) + vertex_offset
+            bend[k] = deck.value(tok, 3, "beam constant is negative")
+            for d in range(ndim):
+                try:
+                    curv[k, d] = float(tok[4 + d])
+                except (IndexError, ValueError):
+                    if d > 0:
+                        raise deck.invalid("incomplete beam curvature specification") from None
+                    break
+            if uniform_bend_rigidity is not None:
+                bend[k] = uniform_bend_rigidity
+            if ucurv is not None:
+                curv[k] = ucurv
+    return BeamDeck(mastr, nxt, prev, bend, curv)
+
+
+def read_target(path: str | os.PathLike, num_vertex: int, vertex_offset: int = 0,
+                uniform_target_stiffness: Optional[float] = None,
+                uniform_target_damping: Optional[float] = None) -> TargetDeck:
+    """Read a ``.target`` file: per line ``idx kappa [eta]``; a missing damping column is 0.
+
+    Follows IBStandardInitializer::readTargetPointFiles (IBStandardInitializer.cpp:
+    1740-1870).  The reference keeps one specification per vertex of the structure (zero
+    where the file names none; a vertex named twice keeps its last line), and a uniform
+    override sets it on every vertex (:1857-1870): with one given, the result covers
+    vertices ``0 .. num_vertex-1`` in index order; otherwise the vertices the file names.
+    """
+    spec: dict = {}
+    with _Deck(path, "target point") as deck:
+        n = deck.count()
+        for _ in range(n):
+            tok = deck.tokens()
+            i = deck.index(tok, 0, num_vertex)
+            k = deck.value(tok, 1, "target point spring constant is negative")
+            e = 0.0
+            if len(tok) > 2:
+                try:
+                    e = float(tok[2])
+                except ValueError:
+                    e = 0.0
+                if e < 0.0:
+                    raise deck.invalid("target point damping coefficient is negative")
+            spec[i] = (k, e)
+    if uniform_target_stiffness is not None or uniform_target_damping is not None:
+        spec = {i: spec.get(i, (0.0, 0.0)) for i in range(num_vertex)}
+    node = np.fromiter(spec.keys(), dtype=np.int32, count=len(spec)) + np.int32(vertex_offset)
+    kappa = np.array([v[0] for v in spec.values()], dtype=np.float64)
+    eta = np.array([v[1] for v in spec.values()], dtype=np.float64)
+    if uniform_target_stiffness is not None:
+        kappa[:] = uniform_target_stiffness
+    if uniform_target_damping is not None:
+        eta[:] = uniform_target_damping
+    return TargetDeck(node, kappa, eta)
+
+
+def _write_deck(path, rows: List[str]) -> None:
+    if not rows:
+        raise ValueError("a deck holds at least one entry")
+    with open(os.fspath(path), "w") as fh:
+        fh.write(f"{len(rows)}\n")
+        fh.write("\n".join(rows) + "\n")
+
+
+def write_spring(path: str | os.PathLike, mastr, slave, kappa, rest, fcn_idx=None, extra=None) -> None:
+    """Write a ``.spring`` file (``%.16e``: a read gives the same doubles back).  The
+    function index column is written when ``fcn_idx`` or ``extra`` is given."""
+    n = len(mastr)
+    rows = []
+    for k in range(n):
+        row = f"{int(mastr[k]):6d} {int(slave[k]):6d} {float(kappa[k]):.16e} {float(rest[k]):.16e}"
+        if fcn_idx is not None or extra is not None:
+            row += f" {int(fcn_idx[k]) if fcn_idx is not None else 0:d}"
+            if extra is not None:
+                row += "".join(f" {float(v):.16e}" for v in extra[k])
+        rows.append(row)
+    _write_deck(path, rows)
+
+
+def write_beam(path: str | os.PathLike, mastr, next, prev, bend, curv=None) -> None:
+    """Write a ``.beam`` file (columns prev, mastr, next, bend and, if given, the curvature)."""
+    rows = []
+    for k in range(len(mastr)):
+        row = f"{int(prev[k]):6d} {int(mastr[k]):6d} {int(next[k]):6d} {float(bend[k]):.16e}"
+        if curv is not None:
+            row += "".join(f" {float(v):.16e}" for v in curv[k])
+        rows.append(row)
+    _write_deck(path, rows)
+
+
+def write_target(path: str | os.PathLike, node, kappa, eta=None) -> None:
+    """Write a ``.target`` file (``idx kappa`` and, if given, the damping column)."""
+    rows = []
+    for k in range(len(node)):
+        row = f"{int(node[k]):6d} {float(kappa[k]):.16e}"
+        if eta is not None:
+            row += f" {float(eta[k]):.16e}"
+        rows.append(row)
+    _write_deck(path, rows)
 
 
 def _aligned(nbytes: int, align: int) -> int:

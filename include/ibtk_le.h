@@ -503,6 +503,54 @@ enum { IBTK_LE_EULER = 0, IBTK_LE_MIDPOINT = 1, IBTK_LE_TRAPEZOIDAL = 2 };
 int ibtk_le_position_update(ibtk_le_ctx ctx, int scheme, long long n, double dt, const double* X_cur_dev,
                             const double* U0_dev, const double* U1_dev, double* X_new_dev);
 
+/* ---- Lagrangian force generation (IBStandardForceGen) ------------------------------
+ * The F handed to spread: the sum of spring, beam and target-point forces
+ * IBStandardForceGen::computeLagrangianForce (IBStandardForceGen.cpp:265-313) computes
+ * from X and U between the position update and the spread.  The reference zeroes a
+ * scratch vector F_ghost, adds the springs (:778-892), the beams (:990-1099) and the
+ * target points (:1150-1216) into it, each in a serial loop over k, and then adds
+ * F_ghost to F.  At positions x = X + dX (dX: the nodes' periodic displacements, :289):
+ *   spring k (master m, slave s, kappa, L):  D = x[s] - x[m], R = sqrt(D.D) summed left
+ *     to right, skipped when R < DBL_EPSILON; f = ((kappa (R - L)) / R) D;
+ *     F[m] += f, F[s] -= f      (the default law, IBSpringForceFunctions.h:117-120)
+ *   beam k (master m, next, prev, K, C):     f = K (((x[next] + x[prev]) - 2 x[m]) - C);
+ *     F[m] += 2 f, F[next] -= f, F[prev] -= f
+ *   target point k (node i, K, E, X0):       F[i] += K (X0 - x[i]) - E U[i]
+ * The plan keeps, per node, the list of its contributions in that order (springs by k,
+ * then beams by k -- master, next, prev within one k --, then target points by k), and
+ * one gather kernel, a lane per node, evaluates every contribution from the reference's
+ * operands with the reference's operations and sums them in list order: no atomics, the
+ * serial loops' result bit for bit.  A node with a very long list runs serially in its
+ * lane.
+ *
+ * The set_* calls take HOST arrays of NODE indices in [0, n_nodes) -- the vectors
+ * IBStandardForceGen caches in d_spring_data / d_beam_data / d_target_point_data before
+ * its multiply by NDIM (petsc_*_node_idxs / NDIM) --, validate them
+ * (IBTK_LE_ERR_ARG: an index out of range, mastr == slave / next / prev, which the
+ * reference asserts against, a negative count, a NULL fg, a non-zero spring force
+ * function index: only the default Hookean law runs on the device, registered host
+ * function pointers do not) and replace that class of the plan (n = 0 clears it); they
+ * block until the plan is on the device.  A failed call leaves the plan as it was.  Row
+ * offsets are 64-bit, so no count an int can hold overflows them (IBTK_LE_ERR_RANGE is
+ * never needed).  n_nodes may include trailing ghost nodes; the library does not
+ * distinguish them.  fcn_idx, curv and eta may be NULL (all zero). */
+typedef struct ibtk_le_forcegen_s* ibtk_le_forcegen;
+int ibtk_le_forcegen_create(ibtk_le_ctx ctx, int ndim, int n_nodes, ibtk_le_forcegen* out);
+int ibtk_le_forcegen_destroy(ibtk_le_forcegen fg);
+int ibtk_le_forcegen_set_springs(ibtk_le_forcegen fg, int n, const int* mastr, const int* slave, const double* kappa,
+                                 const double* rest, const int* fcn_idx);
+int ibtk_le_forcegen_set_beams(ibtk_le_forcegen fg, int n, const int* mastr, const int* next, const int* prev,
+                               const double* bend, const double* curv);
+int ibtk_le_forcegen_set_targets(ibtk_le_forcegen fg, int n, const int* node, const double* kappa, const double* eta,
+                                 const double* X0);
+/* F = F + acc (accumulate != 0) or F = acc on [n_nodes][ndim] device arrays, ordered on
+ * the context stream: no host synchronisation, no allocation.  dX_dev may be NULL (zero
+ * displacements); U_dev may be NULL (read as zero) unless some target point has
+ * eta != 0.  With nothing set, F is left untouched when accumulating and zeroed
+ * otherwise.  F must not alias X, dX or U. */
+int ibtk_le_forcegen_compute(ibtk_le_ctx ctx, ibtk_le_forcegen fg, const double* X_dev, const double* dX_dev,
+                             const double* U_dev, double* F_dev, int accumulate);
+
 /* Position update fused with the z-slab migration classes (bench.py --move, ibamr_amd.slab.
  * migrate_device): X_new = the ibtk_le_position_update of (X_cur, U0, U1), wrapped
  * into [0, L) per dim as torch.remainder does; the markers' owners are the slabs of
