@@ -7,16 +7,19 @@
  * only as the checker / the timed CPU baseline; the product library
  * (ibamr_amd/lib/libibtk_le.so) never links, calls or falls back to it.
  *
- * PARITY STATUS: "parity unpinned" against the reference binary.  The
- * reference routines live in
+ * PARITY STATUS: pinned to the reference's own Fortran.  The reference routines
+ * live in
  *   ibtk/src/lagrangian/fortran/lagrangian_interaction{2,3}d.f.m4
  *   ibtk/src/lagrangian/fortran/lagrangian_delta.f.m4
- * and need the m4 macro processor (absent from this image) plus SAMRAI's
- * pdat_m4arrdim{2,3}d.i (not vendored) to build, so they cannot be compiled
- * here without writing stand-ins; the reference ships no tests, fixtures or
- * recorded outputs for this path.  The restatement is pinned
- * instead by the kernels' published analytic identities and hand-derived
- * known-answer vectors (tests/golden/, tests/test_oracle_*.py).
+ * oracle/build_ref.py expands their few m4 macros and compiles them with flang
+ * into oracle/_ref/ (never committed); tests/test_ref_pin.py holds this file
+ * bitwise equal to that library at -O0 (IB_6 at -O2 only within 1e-13 / 1e-12:
+ * the order of its integer powers is the compiler's).  Two deliberate
+ * deviations are kept apart from the pin: DISCONTINUOUS_LINEAR 3-D spread and
+ * PIECEWISE_CONSTANT markers outside the ghost box (both noted below).  The
+ * reference ships no tests, fixtures or recorded outputs for this path
+ * (SURVEY.md F4); the kernels' published analytic identities and hand-derived
+ * known-answer vectors (tests/golden/, tests/test_oracle_*.py) hold it too.
  *
  * Every routine follows the Fortran text operation by operation (loop order,
  * left-to-right association, NINT = round-half-away-from-zero, division by dx,

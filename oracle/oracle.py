@@ -4,8 +4,14 @@ Only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s ``cpu_baseline``
 leg may import this module, and only as the checker (or the timed CPU
 baseline).  The product path (``ibamr_amd``) never imports it.
 
-Parity status: **parity unpinned** against the reference binary (the Fortran
-needs m4 + SAMRAI's ``pdat_m4arrdim*.i``, both absent).
+Parity status: **pinned** to the reference's own Fortran, compiled by
+``oracle/build_ref.py`` into ``oracle/_ref/`` (``tests/test_ref_pin.py``): bitwise at
+``-O0`` for all eight Fortran kernels; at ``-O2`` bitwise for seven, IB_6 within
+1e-13 / 1e-12 (the order of its integer powers is the compiler's).  Kept apart:
+``DISCONTINUOUS_LINEAR`` 3-D spread (the reference reads an unset ``ic_center``) and
+``PIECEWISE_CONSTANT`` markers outside the ghost box (the reference has no check; here
+they are skipped).  BSPLINE_4, USER_DEFINED, the C++ wrappers and the force generator
+stay unpinned: they need SAMRAI.  See DESIGN.md §Oracle.
 The arithmetic lives in ``le_oracle.c`` (a restatement of
 ``ibtk/src/lagrangian/fortran/lagrangian_interaction{2,3}d.f.m4``); this module
 adds ctypes bindings and restates the C++ wrappers around it:
@@ -219,12 +225,19 @@ def side_box(box_lo, box_hi, axis):
     return list(box_lo), hi
 
 
-def side_interp(kernel, dx, x_lower, box_lo, box_hi, gcw, u_axes, indices, Xshift, X, Q):
+def _raw(backend):
+    """The raw (interp, spread) pair the wrapper restatements run over: this module's
+    own by default, or e.g. ``oracle.ref.backend()`` (the compiled reference Fortran)."""
+    return (interp, spread) if backend is None else backend
+
+
+def side_interp(kernel, dx, x_lower, box_lo, box_hi, gcw, u_axes, indices, Xshift, X, Q, backend=None):
     """LEInteractor::interpolate on SideData (LEInteractor.cpp:1017-1053).
 
     u_axes[a] is the ghosted side array of axis a; Q is AoS (M, NDIM), written
     at the listed markers only.
     """
+    interp = _raw(backend)[0]
     ndim = len(box_lo)
     idx = _i32(indices)
     if idx.size == 0:
@@ -240,8 +253,9 @@ def side_interp(kernel, dx, x_lower, box_lo, box_hi, gcw, u_axes, indices, Xshif
     return Q
 
 
-def side_spread(kernel, dx, x_lower, box_lo, box_hi, gcw, u_axes, indices, Xshift, X, Q):
+def side_spread(kernel, dx, x_lower, box_lo, box_hi, gcw, u_axes, indices, Xshift, X, Q, backend=None):
     """LEInteractor::spread on SideData (LEInteractor.cpp:1876-1911)."""
+    spread = _raw(backend)[1]
     ndim = len(box_lo)
     idx = _i32(indices)
     if idx.size == 0:
@@ -258,26 +272,26 @@ def side_spread(kernel, dx, x_lower, box_lo, box_hi, gcw, u_axes, indices, Xshif
     return u_axes
 
 
-def cell_interp(kernel, dx, x_lower, box_lo, box_hi, gcw, u, indices, Xshift, X, Q, depth):
+def cell_interp(kernel, dx, x_lower, box_lo, box_hi, gcw, u, indices, Xshift, X, Q, depth, backend=None):
     """LEInteractor::interpolate on CellData (LEInteractor.cpp:1058-1146 -> private :2399)."""
-    return interp(kernel, dx, x_lower, box_lo, box_hi, gcw, u, indices, Xshift, X, Q, depth=depth)
+    return _raw(backend)[0](kernel, dx, x_lower, box_lo, box_hi, gcw, u, indices, Xshift, X, Q, depth=depth)
 
 
-def cell_spread(kernel, dx, x_lower, box_lo, box_hi, gcw, u, indices, Xshift, X, Q, depth):
-    return spread(kernel, dx, x_lower, box_lo, box_hi, gcw, u, indices, Xshift, X, Q, depth=depth)
+def cell_spread(kernel, dx, x_lower, box_lo, box_hi, gcw, u, indices, Xshift, X, Q, depth, backend=None):
+    return _raw(backend)[1](kernel, dx, x_lower, box_lo, box_hi, gcw, u, indices, Xshift, X, Q, depth=depth)
 
 
-def node_interp(kernel, dx, x_lower, box_lo, box_hi, gcw, u, indices, Xshift, X, Q, depth):
+def node_interp(kernel, dx, x_lower, box_lo, box_hi, gcw, u, indices, Xshift, X, Q, depth, backend=None):
     """NodeData: x_lower -= dx/2 in every dim, NodeGeometry::toNodeBox (upper + 1)."""
     xl = [x_lower[d] - 0.5 * dx[d] for d in range(len(box_lo))]
     hi = [h + 1 for h in box_hi]
-    return interp(kernel, dx, xl, box_lo, hi, gcw, u, indices, Xshift, X, Q, depth=depth)
+    return _raw(backend)[0](kernel, dx, xl, box_lo, hi, gcw, u, indices, Xshift, X, Q, depth=depth)
 
 
-def node_spread(kernel, dx, x_lower, box_lo, box_hi, gcw, u, indices, Xshift, X, Q, depth):
+def node_spread(kernel, dx, x_lower, box_lo, box_hi, gcw, u, indices, Xshift, X, Q, depth, backend=None):
     xl = [x_lower[d] - 0.5 * dx[d] for d in range(len(box_lo))]
     hi = [h + 1 for h in box_hi]
-    return spread(kernel, dx, xl, box_lo, hi, gcw, u, indices, Xshift, X, Q, depth=depth)
+    return _raw(backend)[1](kernel, dx, xl, box_lo, hi, gcw, u, indices, Xshift, X, Q, depth=depth)
 
 
 def get_cell_index(X, x_lower, x_upper, dx, ilower, iupper):

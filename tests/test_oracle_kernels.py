@@ -4,8 +4,8 @@ Pins the restatement with (1) known-answer weights computed in 60-digit decimal
 from the reference's own 1-D delta functions (tests/golden/kernel_weights.json,
 made by tests/golden/make_golden.py) and (2) the analytic identities the
 kernels are built to satisfy.  The reference has no test suite
-of its own for this path, and its Fortran cannot be built here, so the oracle
-is "parity unpinned" against the reference binary.
+of its own for this path; tests/test_ref_pin.py pins the oracle to the
+reference's compiled Fortran where that can be built.
 """
 import json
 from decimal import Decimal
