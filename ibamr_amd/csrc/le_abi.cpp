@@ -2066,6 +2066,11 @@ extern "C" int ibtk_le_level_fill_interp(ibtk_le_ctx ctx, ibtk_le_markers m, int
     if (!ctx || !m || !q_dev) return fail(IBTK_LE_ERR_ARG, "level_fill_interp: null argument");
     if (m->npatch <= 0) return fail(IBTK_LE_ERR_ARG, "level_fill_interp: not a level binning (ibtk_le_level_bin)");
     const int np = m->npatch;
+    {  // what ibtk_le_level_interp refuses is refused before the fill writes a ghost
+        const int nc = ncomponents(&m->geoms[0], centering, q_depth, Q_depth);
+        if (nc < 0) return -nc;
+        if (nc > MAXC) return fail(IBTK_LE_ERR_ARG, "level calls take at most %d components", MAXC);
+    }
     auto unfused = [&]() {
         if (int rc = ibtk_le_level_fill_ghosts(ctx, np, m->geoms.data(), centering, q_dev, q_depth, periodic)) return rc;
         return ibtk_le_level_interp(ctx, m, kernel, centering, axis, q_dev, q_depth, Q_dev, Q_depth, X_dev);

@@ -161,6 +161,10 @@ class Context:
         check(self.lib.ibtk_le_ctx_create(device, ctypes.c_void_p(s.cuda_stream), ctypes.byref(h)))
         self.h = h
         self.plane_window = (0, 0, -1)
+        # open Markers of this context: their library handles point to it, so it is
+        # destroyed after the last of them (a collector may finalise it before them)
+        self._live = 0
+        self._closing = False
 
     def set_stream(self, stream: torch.cuda.Stream):
         self.stream = stream
@@ -198,6 +202,9 @@ class Context:
 
     def close(self):
         if getattr(self, "h", None):
+            if self._live > 0:  # closed by the last of its markers
+                self._closing = True
+                return
             self.lib.ibtk_le_ctx_destroy(self.h)
             self.h = None
 
@@ -220,6 +227,7 @@ class Markers:
         h = ctypes.c_void_p()
         check(ctx.lib.ibtk_le_markers_create(ctx.h, ctypes.byref(h)))
         self.h = h
+        ctx._live += 1
         self.kernel = None
         self.geom = None
 
@@ -283,6 +291,9 @@ class Markers:
         if getattr(self, "h", None):
             self.ctx.lib.ibtk_le_markers_destroy(self.h)
             self.h = None
+            self.ctx._live -= 1
+            if self.ctx._closing and self.ctx._live == 0:
+                self.ctx.close()
 
     def __del__(self):
         # at interpreter exit the HIP runtime may already be torn down: leave the
@@ -967,7 +978,12 @@ def mark_stencils(ctx: Context, markers: Markers, kernel: str, centering: str, g
     """uint8 masks (one per component, shaped like the arrays) of the points some stencil touches."""
     masks = [torch.zeros(geom.array_shape(centering, c, q_depth), dtype=torch.uint8, device=X.device)
              for c in range(geom.ncomp(centering))]
-    arr = (ctypes.c_void_p * len(masks))(*[m.data_ptr() for m in masks])
+    if centering in ("cell", "node"):
+        # the library takes one mask per component: depth k of the one cell/node mask
+        ptrs = [masks[0].data_ptr() + k * masks[0][0].numel() for k in range(q_depth)]
+    else:
+        ptrs = [m.data_ptr() for m in masks]
+    arr = (ctypes.c_void_p * max(1, len(ptrs)))(*ptrs)
     check(ctx.lib.ibtk_le_mark_stencils(ctx.h, markers.h, kernel_id(kernel), CENTERING[centering], axis,
                                         ctypes.byref(geom.c), arr, q_depth, _ptr(X)))
     return masks

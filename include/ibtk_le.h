@@ -145,7 +145,8 @@ int ibtk_le_ctx_synchronize(ibtk_le_ctx ctx);
  * NULL/NULL for the identity list 0..n-1 with zero shifts -- and sorts it on the
  * device by the stencil anchor cell of X(s)+Xshift (stable radix sort; 3-D:
  * buckets of (anchor plane, 32x16-cell column, reach band); 2-D: bricks of 16^2
- * cells).  The handle keeps device copies of the sorted list. */
+ * cells).  The handle keeps device copies of the sorted list, and a pointer to its
+ * context: destroy a context's markers before the context. */
 int ibtk_le_markers_create(ibtk_le_ctx ctx, ibtk_le_markers* out);
 int ibtk_le_markers_destroy(ibtk_le_markers m);
 int ibtk_le_markers_bin(ibtk_le_ctx ctx, ibtk_le_markers m, const ibtk_le_patch_geom* geom, int kernel,
@@ -243,7 +244,10 @@ int ibtk_le_spread_ds(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, int center
  * interior list for interp, the ghost-box list for spread, as LDataManager uses.
  * q_dev: the arrays of patch 0, then patch 1, ... (NDIM per patch for SIDE/EDGE,
  * one for CELL/NODE).  Results equal the per-patch calls' (interp bit for bit;
- * spread in each patch's own fixed order). */
+ * spread in each patch's own fixed order).
+ * Limit: a level interp / spread / zero_spread / fill_interp takes at most 4
+ * components (CELL / NODE: q_depth <= 4); more returns IBTK_LE_ERR_ARG ("level calls
+ * take at most 4 components") and writes nothing. */
 int ibtk_le_level_bin(ibtk_le_ctx ctx, ibtk_le_markers m, int npatch, const ibtk_le_patch_geom* geoms, int kernel,
                       const double* X_dev, const int* entry_offsets, const int* indices_dev,
                       const double* Xshift_dev);
@@ -299,7 +303,9 @@ int ibtk_le_level_fill_ghosts(ibtk_le_ctx ctx, int npatch, const ibtk_le_patch_g
  * copies nothing, the patch's own ghost values are read).  Fused when, per component, every patch's array lies within one 2-GB
  * address window (one allocation per component for the level, e.g.), the patches have
  * at least 32 + W - 1 cells in x and 16 + W - 1 in y (W: the kernel's stencil width),
- * and the data are SIDE or CELL of depth 1; otherwise the two calls. */
+ * and the data are SIDE or CELL of depth 1; otherwise the two calls (NODE and EDGE data:
+ * ibtk_le_level_fill_ghosts' IBTK_LE_ERR_ARG, "side or cell data", nothing written).
+ * More than 4 components are refused before the fill writes a ghost. */
 int ibtk_le_level_fill_interp(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, int centering, int axis,
                               double* const* q_dev, int q_depth, double* Q_dev, int Q_depth, const double* X_dev,
                               const int* periodic);
@@ -321,7 +327,10 @@ int ibtk_le_fill_interp(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, int cent
  * interior markers, then fold every ghost value back onto its periodic interior
  * image (dims folded slowest first, one source per destination per pass:
  * deterministic).  The multi-GPU path uses the same fold along x/y and an RCCL
- * exchange along z. */
+ * exchange along z.
+ * Limit: ibtk_le_fill_periodic_ghosts, ibtk_le_zero_ghosts and
+ * ibtk_le_fold_periodic_ghosts take at most 16 arrays a call (CELL / NODE: q_depth
+ * <= 16); more returns IBTK_LE_ERR_ARG ("too many arrays") and writes nothing. */
 int ibtk_le_zero_ghosts(ibtk_le_ctx ctx, const ibtk_le_patch_geom* geom, int centering, double* const* q_dev,
                         int q_depth);
 /* ibtk_le_zero_ghosts followed by ibtk_le_spread, bit for bit, in one sweep for a 3-D
@@ -587,7 +596,10 @@ int ibtk_le_slab_migrate_unpack(ibtk_le_ctx ctx, const double* rows_dev, int dep
 
 /* Diagnostics: masks_dev[c] (one byte per point of component c's ghosted array,
  * same layout) gets 1 at every point some listed stencil touches after clipping.
- * bench.py sums the masks for the exact algorithmic byte count |S_a|. */
+ * bench.py sums the masks for the exact algorithmic byte count |S_a|.
+ * One mask pointer per component, packed whatever geom's pitch: NDIM for SIDE / EDGE,
+ * q_depth for CELL / NODE (masks_dev[k]: depth k).  Limit: at most 4 components; more
+ * returns IBTK_LE_ERR_ARG ("mark_stencils: at most 4 components"). */
 int ibtk_le_mark_stencils(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, int centering, int axis,
                           const ibtk_le_patch_geom* geom, unsigned char* const* masks_dev, int q_depth,
                           const double* X_dev);
