@@ -193,6 +193,8 @@ struct ibtk_le_markers_s {
     // a binning: 0 stale, 1 built, 2 stale unless the last re-binning moved nothing (the
     // build then skips on the device, cs_skip = that re-binning's mover count)
     DevBuf cs_cnt, cs_off, cs_pos;
+    DevBuf cs_src;            // beside cs_pos, the entries' marker rows (Params::cs_src; f_stream)
+    bool cs_has_src = false;  // the stream as built holds them
     int cs_state = 0;
     const int* cs_skip = nullptr;
     // closed-form kernels: the stream split by the shifted-z anchor and its boundaries in
@@ -337,6 +339,7 @@ extern "C" int ibtk_le_ctx_tune(ibtk_le_ctx ctx, const char* key, int value) {
     else if (k == "xcd_block") t.xcd_block = value;
     else if (k == "interp3") t.interp3 = value;
     else if (k == "side_gather") t.side_gather = value;
+    else if (k == "f_stream") t.f_stream = value;
     else return fail(IBTK_LE_ERR_ARG, "unknown tuning key %s", key);
     return IBTK_LE_OK;
 }
@@ -596,7 +599,7 @@ extern "C" int ibtk_le_markers_destroy(ibtk_le_markers m) {
                       &m->nsub, &m->isub, &m->nitems, &m->pd, &m->entry_off, &m->qin, &m->owner, &m->int_off,
                       &m->rb_cin, &m->rb_cout, &m->rb_d, &m->rb_dpre, &m->rb_mstart, &m->rb_ps2, &m->rb_mbits,
                       &m->rb_wcnt, &m->rb_wpre, &m->rb_mlist, &m->rb_scr, &m->rb_big, &m->rb_nbig, &m->cs_cnt,
-                      &m->cs_off, &m->cs_pos, &m->cs_off_z, &m->zbits, &m->zst, &m->sel_gs})
+                      &m->cs_off, &m->cs_pos, &m->cs_src, &m->cs_off_z, &m->zbits, &m->zst, &m->sel_gs})
         b->release();
     delete m;
     return IBTK_LE_OK;
@@ -1214,9 +1217,16 @@ static int build_candidates(ibtk_le_ctx ctx, ibtk_le_markers m, const Params& p)
 // Worth its cross-stream hops (about 0.05 ms a step) only on a large gather: cfg4 (1e8
 // markers) gains 0.2 ms, cfg5 (1e7, a level) loses 0.04 ms; the gain scales with n, even
 // at about 2.5e7.  side_gather: 0 auto (n >= 2^25), 1 always, -1 never.
+// The gather pass itself is the alternative (f_stream -1) to the 3-D sweep reading F at its
+// marker row through the candidate stream's source rows (f_stream 1, Params::cs_src): no
+// sorted_F, no pass, no side stream.  f_stream 0, the default, is 1 (cfg4: the 1.2-ms pass
+// goes, the sweep gives 0.4 ms back).
+static bool f_stream(ibtk_le_ctx ctx, ibtk_le_markers) {
+    return ctx->tune.f_stream >= 0;
+}
 static bool side_gather(ibtk_le_ctx ctx, ibtk_le_markers m) {
     const int t = ctx->tune.side_gather;
-    return t > 0 || (t == 0 && m->n >= (1 << 25));
+    return !f_stream(ctx, m) && (t > 0 || (t == 0 && m->n >= (1 << 25)));
 }
 static int gather_fork(ibtk_le_ctx ctx, const Params& p) {
     if (!ctx->side) {  // created together, or not at all
@@ -1476,14 +1486,15 @@ extern "C" int ibtk_le_user_spread(ibtk_le_ctx ctx, int centering, int axis, con
 // centerings were spread since it (advisor, round 5)
 static bool cand_split(int k) { return k == K_IB_4 || k == K_BSPLINE_4 || k == K_IB_6 || k == K_IB_4_W8; }
 // the stream stands as built: cand_stream launches nothing
-static bool cand_stream_built(ibtk_le_markers m) {
-    return m->cs_state == 1 && m->cs_pos.p && (m->cs_split || !cand_split(m->kernel));
+static bool cand_stream_built(ibtk_le_markers m, bool src) {
+    return m->cs_state == 1 && m->cs_pos.p && (m->cs_split || !cand_split(m->kernel)) && (!src || m->cs_has_src);
 }
 static int cand_stream(ibtk_le_ctx ctx, ibtk_le_markers m, Params& p) {
     const long long ncl = (long long)m->nbuckets_total / NBAND;
     const long long nclz = m->npatch ? m->nclz : (long long)m->cg.ncol * (m->cg.nz + 1);
     const int k = m->kernel;
     const bool split = cand_split(k);
+    const bool src = f_stream(ctx, m);  // the entries' marker rows beside their positions (Params::cs_src)
     // A marker is a candidate of at most four columns (its own, one x- and one y-neighbour,
     // the corner between them: a stencil never reaches both neighbours in a dim), so 4 n
     // positions always hold the stream (16 bytes a marker; about 1.3 of the 4 are used by
@@ -1494,19 +1505,22 @@ static int cand_stream(ibtk_le_ctx ctx, ibtk_le_markers m, Params& p) {
         return fail(IBTK_LE_ERR_RANGE, "candidate stream too long");
     p.cs_off = m->cs_off.as<int>();
     p.cs_pos = m->cs_pos.as<int>();
+    p.cs_src = src ? m->cs_src.as<int>() : nullptr;
     p.cs_total = (int)cap;
     p.cs_off_z = m->cs_split ? m->cs_off_z.as<int>() : nullptr;
     p.cs_rint = k == K_IB_4 ? 1 : 0;  // the IB_4 spread anchors by rint (spread_setup)
-    if (cand_stream_built(m)) return IBTK_LE_OK;
+    if (cand_stream_built(m, src)) return IBTK_LE_OK;
     int rc;
     // cs_cnt: ncl + 1 counts, then the stream's 64-bit length (8-byte aligned)
     const size_t tot_at = (sizeof(int) * (size_t)(ncl + 1) + 7) / 8 * 8;
     if ((rc = m->cs_cnt.ensure(tot_at + sizeof(unsigned long long)))) return rc;
     if ((rc = m->cs_off.ensure(sizeof(int) * (size_t)(ncl + 1)))) return rc;
     if ((rc = m->cs_pos.ensure(sizeof(int) * (size_t)cap))) return rc;
+    if (src && (rc = m->cs_src.ensure(sizeof(int) * (size_t)cap))) return rc;
     if (split && (rc = m->cs_off_z.ensure(sizeof(int) * (size_t)(nclz + 1)))) return rc;
     p.cs_off = m->cs_off.as<int>();
     p.cs_pos = m->cs_pos.as<int>();
+    p.cs_src = src ? m->cs_src.as<int>() : nullptr;
     p.cs_off_z = split ? m->cs_off_z.as<int>() : nullptr;
     HIP_TRY(hipMemsetAsync(m->cs_cnt.as<int>() + ncl, 0, sizeof(int), ctx->stream));
     size_t tb = 0;
@@ -1515,15 +1529,17 @@ static int cand_stream(ibtk_le_ctx ctx, ibtk_le_markers m, Params& p) {
     Params q = p;
     // (a split stream stands across a re-binning that moved nothing only if no shifted-z
     // anchor changed either: RebinBufs::zst[1])
-    const bool keep = m->cs_state == 2 && (!split || (m->cs_split && m->zst.p));
+    // (nor does a stream without the source rows stand when they are wanted)
+    const bool keep = m->cs_state == 2 && (!split || (m->cs_split && m->zst.p)) && (!src || m->cs_has_src);
     q.items_skip = keep ? m->cs_skip : nullptr;
     q.cs_zflip = m->zst.p ? m->zst.as<int>() + 1 : nullptr;
     q.cs_epoch = m->rb_epoch;
-    HIP_TRY(launch_cand_stream(q, (int)ncl, m->cs_cnt.as<int>(), m->cs_off.as<int>(), m->cs_pos.as<int>(), ctx->temp.p,
-                               ctx->temp.cap,
+    HIP_TRY(launch_cand_stream(q, (int)ncl, m->cs_cnt.as<int>(), m->cs_off.as<int>(), m->cs_pos.as<int>(),
+                               src ? m->cs_src.as<int>() : nullptr, ctx->temp.p, ctx->temp.cap,
                                reinterpret_cast<unsigned long long*>(m->cs_cnt.as<char>() + tot_at), ctx->stream));
     m->cs_state = 1;
     m->cs_split = split;
+    m->cs_has_src = src;
     return IBTK_LE_OK;
 }
 
@@ -1543,7 +1559,8 @@ static int spread_impl(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, int cente
     p.ds = ds_dev;
     p.Q_depth = Q_depth;
     p.nsorted = m->n;
-    {
+    p.sorted_F = nullptr;
+    if (geom->ndim == 2 || !f_stream(ctx, m)) {  // (f_stream: the 3-D sweep reads Q at its rows)
         if (int rc = ctx->fbuf.ensure(sizeof(double) * (size_t)m->n * (size_t)std::min(nc, MAXC))) return rc;
         p.sorted_F = ctx->fbuf.as<double>();
     }
@@ -1556,7 +1573,7 @@ static int spread_impl(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, int cente
     for (int first = 0; first < nc; first += MAXC) {
         const int cnt = std::min(MAXC, nc - first);
         if (int rc = make_comps(geom, centering, axis, q_dev, q_depth, Q_depth, first, cnt, p)) return rc;
-        const bool side = geom->ndim == 3 && side_gather(ctx, m) && !cand_stream_built(m);
+        const bool side = geom->ndim == 3 && side_gather(ctx, m) && !cand_stream_built(m, false);
         if (side)
             if (int rc = gather_fork(ctx, p)) return rc;
         if (geom->ndim == 3)
@@ -1910,11 +1927,12 @@ static int level_spread_impl(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, int
     if (!Q_dev) return fail(IBTK_LE_ERR_ARG, "null Q");
     p.Qin = Q_dev;
     p.zero_first = zero_first ? 1 : 0;
-    {
+    p.sorted_F = nullptr;
+    if (!f_stream(ctx, m)) {  // (f_stream: the sweep reads Q at its rows)
         if (int rc = ctx->fbuf.ensure(sizeof(double) * (size_t)m->n * (size_t)nc)) return rc;
         p.sorted_F = ctx->fbuf.as<double>();
     }
-    const bool side = side_gather(ctx, m) && !cand_stream_built(m);
+    const bool side = side_gather(ctx, m) && !cand_stream_built(m, false);
     if (side)
         if (int rc = gather_fork(ctx, p)) return rc;
     if (int rc = cand_stream(ctx, m, p)) return rc;

@@ -119,6 +119,9 @@ struct SweepTune {
     int side_gather = 0;   // 3-D spread: the F gather on the side stream beside the candidate-stream
                            // rebuild (1), in line before the sweep (-1), or 0 (the default): on
                            // the side stream from 2^25 markers
+    int f_stream = 0;      // 3-D spread: F read at its marker row through the candidate stream's source
+                           // rows (1), gathered into sorted order by a pass before the sweep (-1), or 0:
+                           // the default, which is 1
 };
 // One 3-D sweep item: a patch, a column and its owned planes [p0, p1) (relative
 // to the patch's cg.org[2]).
@@ -177,6 +180,8 @@ struct Params {
     const int* cand_idx;       // spread: candidate sorted positions, canonical order per super-brick
     const int* cs_off;         // 3-D spread: candidate stream offsets per column-anchor (launch_cand_stream)
     const int* cs_pos;         // 3-D spread: the candidate stream (sorted positions)
+    const int* cs_src = nullptr;  // beside cs_pos: the marker row of each entry, sorted_s[cs_pos[j]] (k_cand_write);
+                               // the sweep then reads F at its row.  nullptr: sorted_F (launch_gather_F)
     int cs_total;              // its length
     const int* cs_off_z;       // closed-form kernels: the stream's boundaries per anchor of the frame
                                // shifted by -dz/2 in z (side-z, node, x/y-edge components; k_cand_write)
@@ -340,8 +345,9 @@ hipError_t launch_item_table(int kernel, const Params& p, int target, int heavy,
 // anchor and p.cs_off_z[Σ ncol (nz + 1) + 1] written (k_cand_write; no skip)
 // total: a device u64 for the stream's length in 64 bits (a stream longer than p.cs_total
 // raises device flag 16 and is not written)
-hipError_t launch_cand_stream(const Params& p, int ncl, int* cnt, int* off, int* pos, void* temp, size_t temp_bytes,
-                              unsigned long long* total, hipStream_t s);
+// src (or nullptr): beside pos, the marker row of each entry, p.sorted_s[pos[j]]
+hipError_t launch_cand_stream(const Params& p, int ncl, int* cnt, int* off, int* pos, int* src, void* temp,
+                              size_t temp_bytes, unsigned long long* total, hipStream_t s);
 
 // Periodic helpers
 struct GhostDesc {

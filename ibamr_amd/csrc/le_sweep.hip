@@ -1628,15 +1628,20 @@ struct CaJob {
     Ranges R;
     int e0;     // the lane's first candidate (clamped into the stream piece)
     double z0;  // its z (SHZ)
+    int s0;     // its marker row (src)
 };
 template <bool SHZ>
-__global__ __launch_bounds__(BLOCK) void k_cand_write(Params p, int ncl, const int* off, int* pos,
+__global__ __launch_bounds__(BLOCK) void k_cand_write(Params p, int ncl, const int* off, int* pos, int* src,
                                                       const unsigned long long* total) {
     if (cs_stands(p)) return;
     // a stream of 2^31 entries or more: its 32-bit offsets wrapped; nothing is written and
-    // device flag 16 says so at the next synchronize (the sweeps' reads stay clamped)
+    // device flag 16 says so at the next synchronize (the sweeps' reads stay clamped; the
+    // source rows, which a sweep cannot clamp by value, all name row 0)
     if (*total >= (unsigned long long)p.cs_total + 1ull) {
         if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(p.err, 16);
+        if (src)
+            for (int64_t j = (int64_t)blockIdx.x * BLOCK + threadIdx.x; j < p.cs_total; j += (int64_t)gridDim.x * BLOCK)
+                src[j] = 0;
         return;
     }
     const int lane = threadIdx.x & (SW - 1);
@@ -1663,11 +1668,14 @@ __global__ __launch_bounds__(BLOCK) void k_cand_write(Params p, int ncl, const i
         J.t = 0;
         J.e0 = 0;
         J.z0 = 0.0;
+        J.s0 = 0;
         if (!J.items) return;
         make_ranges_lanes(J.rowv, J.R);
         J.t = J.R.pre[SSh<K_IB_4>::NR];
         J.e0 = range_pos(J.R, min(lane, max(J.t - 1, 0)));
         if constexpr (SHZ) J.z0 = sX[(int64_t)3 * min(J.e0, p.nsorted - 1) + 2];  // (t = 0: e0 may be n)
+        // (the marker row is loaded with z, unconditionally: no further level of dependent loads)
+        if (src) J.s0 = p.sorted_s[min(J.e0, p.nsorted - 1)];
     };
     auto finish = [&](int ca, CaJob& J) {
         if (ca >= ncl) return;
@@ -1680,16 +1688,21 @@ __global__ __launch_bounds__(BLOCK) void k_cand_write(Params p, int ncl, const i
         if constexpr (!SHZ) {
             if (lane < t) pos[o + lane] = J.e0;
             for (int j = lane + SW; j < t; j += SW) pos[o + j] = range_pos(J.R, j);
+            if (src) {  // (after the positions' stores are issued: they do not wait for the rows)
+                if (lane < t) src[o + lane] = J.s0;
+                for (int j = lane + SW; j < t; j += SW) src[o + j] = p.sorted_s[min(range_pos(J.R, j), p.nsorted - 1)];
+            }
         } else {
             const int aa = J.a + J.cg.org[2] - J.zilo;  // the key anchor as a shifted-frame NINT
             int nlo = 0, nup = 0;
             for (int j0 = 0; j0 < t; j0 += SW) {
                 const int j = j0 + lane;
-                int e = J.e0;
+                int e = J.e0, ms = J.s0;
                 double z = J.z0;
                 if (j0 > 0) {
                     e = range_pos(J.R, min(j, t - 1));
                     z = sX[(int64_t)3 * e + 2];
+                    if (src) ms = p.sorted_s[min(e, p.nsorted - 1)];
                 }
                 const double xo = (z - J.zxlo) * inv_dz;
                 const int n = p.cs_rint ? (int)__builtin_rint(xo) : d_nint(xo);
@@ -1698,8 +1711,9 @@ __global__ __launch_bounds__(BLOCK) void k_cand_write(Params p, int ncl, const i
                 const unsigned long long bu = __ballot(up), bl = __ballot(in && !up);
                 const unsigned long long below = (1ull << lane) - 1ull;
                 if (in) {
-                    if (up) pos[o + t - 1 - (nup + __popcll(bu & below))] = e;
-                    else pos[o + nlo + __popcll(bl & below)] = e;
+                    const int at = up ? o + t - 1 - (nup + __popcll(bu & below)) : o + nlo + __popcll(bl & below);
+                    pos[at] = e;
+                    if (src) src[at] = ms;
                 }
                 nlo += __popcll(bl);
                 nup += __popcll(bu);
@@ -1714,8 +1728,8 @@ __global__ __launch_bounds__(BLOCK) void k_cand_write(Params p, int ncl, const i
         finish(ca, J);
     }
 }
-hipError_t launch_cand_stream(const Params& p, int ncl, int* cnt, int* off, int* pos, void* temp, size_t temp_bytes,
-                              unsigned long long* total, hipStream_t s) {
+hipError_t launch_cand_stream(const Params& p, int ncl, int* cnt, int* off, int* pos, int* src, void* temp,
+                              size_t temp_bytes, unsigned long long* total, hipStream_t s) {
     if (ncl <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_cand_count, dim3(std::min((ncl + BLOCK - 1) / BLOCK, CS_GRID)), dim3(BLOCK), 0, s, p, ncl,
                        cnt);
@@ -1728,8 +1742,8 @@ hipError_t launch_cand_stream(const Params& p, int ncl, int* cnt, int* off, int*
     if (e != hipSuccess) return e;
     const int per = BLOCK / SW;
     const dim3 g(std::min((ncl + per - 1) / per, CS_GRID)), b(BLOCK);
-    if (p.cs_off_z) hipLaunchKernelGGL(k_cand_write<true>, g, b, 0, s, p, ncl, off, pos, total);
-    else hipLaunchKernelGGL(k_cand_write<false>, g, b, 0, s, p, ncl, off, pos, total);
+    if (p.cs_off_z) hipLaunchKernelGGL(k_cand_write<true>, g, b, 0, s, p, ncl, off, pos, src, total);
+    else hipLaunchKernelGGL(k_cand_write<false>, g, b, 0, s, p, ncl, off, pos, src, total);
     return hipGetLastError();
 }
 
@@ -2051,7 +2065,11 @@ __device__ __forceinline__ void spread_tiled(const Params& p, const CompDesc& cd
 // a+HI+2.  The candidates of anchor a+1 are staged while anchor a is added.
 // CNT: the counted launch of ibtk_le_ctx_count_adds (a kernel of its own name, so
 // profiles of the product sweep do not average it in)
-template <int K, bool LVL, bool CNT, bool ZC>
+// FS: F read at its marker row through the stream's source rows (p.cs_src), not from sorted_F.
+// (A kernel of its own, not a branch on p.cs_src: with the branch around the loads the
+// compiler's waits no longer count them exactly, and the gather path of a level's sweep,
+// whose dense planes run the middle chunks, measured 8-11 % slower than without it.)
+template <int K, bool LVL, bool CNT, bool ZC, bool FS>
 __global__ __launch_bounds__(SW) void k_spread_sweep(Params p) {
     using S = SSh<K, ZC>;
     constexpr int LO = S::LO, HI = S::HIE, NPL = S::NPL, FAM = S::FAM;  // HI: the ring's reach
@@ -2095,7 +2113,8 @@ __global__ __launch_bounds__(SW) void k_spread_sweep(Params p) {
     const int* const cs_offs = shz ? p.cs_off_z : p.cs_off;
     const int ca0 = (LVL ? (shz ? p.pd[si.patch].ca_base_z : p.pd[si.patch].bucket_base / NBAND) : 0) + col * nza + afirst;
     // no candidate reaches the item: u unchanged (zero_first: 0; zero_ghosts: ghosts 0)
-    const bool any = cs_offs[ca0 + (alast - afirst + 1)] > cs_offs[ca0];
+    const int o_end = cs_offs[ca0 + (alast - afirst + 1)];  // the end of the item's stretch
+    const bool any = o_end > cs_offs[ca0];
     // zero_ghosts (ibtk_le_zero_ghosts_spread): the owned points outside the component's
     // data box start from 0 instead of their values -- ibtk_le_zero_ghosts fused in
     const bool zg = p.zero_ghosts && !p.zero_first;
@@ -2140,8 +2159,10 @@ __global__ __launch_bounds__(SW) void k_spread_sweep(Params p) {
         }
         return;
     }
-    // candidate data of sorted position e
-    auto cand_at = [&](int e, Cand& d) {
+    // candidate data of sorted position e, marker row s (the stream's source row beside e;
+    // without FS, s is not used: the value comes from sorted_F and the row from sorted_s)
+    const int* const cs_src = p.cs_src;
+    auto cand_at = [&](int e, int s, Cand& d) {
         e = min(max(e, 0), nlast);  // (an idle lane's stream entry may lie past the stream's end)
 #if IBTK_LE_DIAG_SPREAD & 8  // diagnostic: no candidate loads
         d.X[0] = d.X[1] = d.X[2] = 0.5 + 1e-9 * e;
@@ -2153,8 +2174,14 @@ __global__ __launch_bounds__(SW) void k_spread_sweep(Params p) {
         d.X[0] = xs.v[0];
         d.X[1] = xs.v[1];
         d.X[2] = xs.v[2];
-        d.V = p.sorted_F[(int64_t)c * p.nsorted + e];
-        d.s = FAM == 2 ? p.sorted_s[e] : 0;
+        if constexpr (FS) {  // F at its row: the product k_gather_F_col forms
+            const double v = p.Qin[(int64_t)p.Q_depth * s + cd.qcomp];
+            d.V = p.ds ? v * p.ds[s] : v;
+            d.s = FAM == 2 ? s : 0;
+        } else {
+            d.V = p.sorted_F[(int64_t)c * p.nsorted + e];
+            d.s = FAM == 2 ? p.sorted_s[e] : 0;
+        }
     };
     Clk clk;
     unsigned long long cnt[2] = {0ull, 0ull};  // CNT: wave-uniform totals of the item
@@ -2243,10 +2270,16 @@ __global__ __launch_bounds__(SW) void k_spread_sweep(Params p) {
     // ahead (from the positions loaded at the step before).
     clk.start(p.stamps != nullptr);
     const int* const cs_pos = p.cs_pos;
-    const int cs_last = p.cs_total - 1;
     const int nk = alast - afirst + 1;  // anchors of the item; o(nk) ends its stream
     auto off_load = [&](int k) { return cs_offs[ca0 + min(k, nk)]; };
+    // stream reads are clamped into the item's own stretch (it has an entry: `any`), so
+    // that an idle lane's entry is a written one: a source row cannot be clamped by value
+    const int cs_last = max(min(p.cs_total, __builtin_amdgcn_readfirstlane(o_end)) - 1, 0);
     auto pos_load = [&](int j) { return cs_pos[min(max(j, 0), cs_last)]; };
+    auto src_load = [&](int j) {
+        if constexpr (FS) return cs_src[min(max(j, 0), cs_last)];
+        else return 0;
+    };
     // prologue: planes afirst+LO .. afirst+HI-1 into the ring; plane afirst+HI, the
     // anchor boundaries o(0) .. o(3), chunk 1 of afirst and the positions of chunk 1
     // of afirst + 1 into registers
@@ -2265,10 +2298,13 @@ __global__ __launch_bounds__(SW) void k_spread_sweep(Params p) {
     int N1 = R1 + min(SW - R1, O2 - O1);        // lanes of chunk 1 of k+1
     Cand nxt, nxt2;                             // chunk 1 of k, of k+1
     {
-        const int e0 = pos_load(O0 + min(lane, max(N0 - 1, 0)));
-        cand_at(e0, nxt);
+        const int j0 = O0 + min(lane, max(N0 - 1, 0));
+        const int e0 = pos_load(j0);
+        cand_at(e0, src_load(j0), nxt);
     }
-    int I1 = pos_load(O1 - R1 + min(lane, max(N1 - 1, 0)));  // positions of chunk 1 of k+1, in flight
+    // positions (and source rows) of chunk 1 of k+1, in flight
+    int I1 = pos_load(O1 - R1 + min(lane, max(N1 - 1, 0)));
+    int S1 = src_load(O1 - R1 + min(lane, max(N1 - 1, 0)));
     clk.lap(0);
     // One anchor step: plane a+HI from registers into the ring, plane a+HI+1 into
     // registers.  (Two anchors ahead through two register buffers measured the same,
@@ -2285,6 +2321,7 @@ __global__ __launch_bounds__(SW) void k_spread_sweep(Params p) {
         // vmcnt(0) (the loop-carried copy of a pending load): it then waits for this
         // step's prefetch and writeback too.  cfg4 spread sweep 15.0 -> 13.0 ms (round 5).
         asm volatile("" ::"v"(cur.X[0]), "v"(cur.X[1]), "v"(cur.X[2]), "v"(cur.V), "v"(I1), "v"(O4v));
+        if constexpr (FS) asm volatile("" ::"v"(S1));
         const int O4 = __builtin_amdgcn_readfirstlane(O4v);
         const int cur_r = R0, cur_n = N0;
         const int tCur = O1 - O0;
@@ -2296,11 +2333,12 @@ __global__ __launch_bounds__(SW) void k_spread_sweep(Params p) {
         // chunk 1 of a+2 (a+1's last r, then a+2's first), the boundary o(k+5); plane a+HI+1
         int R2 = 0, N2 = 0;
         if (a + 1 <= alast) {
-            cand_at(I1, nxt);
+            cand_at(I1, S1, nxt);
             const int t1 = O2 - O1;
             R2 = (t1 - min(SW - R1, t1)) % SW;
             N2 = R2 + min(SW - R2, O3 - O2);
             I1 = pos_load(O2 - R2 + min(lane, max(N2 - 1, 0)));
+            S1 = src_load(O2 - R2 + min(lane, max(N2 - 1, 0)));
             O4v = off_load(k + 5);
             plane_load(a + HI + 1, pv);
         }
@@ -2312,34 +2350,38 @@ __global__ __launch_bounds__(SW) void k_spread_sweep(Params p) {
             // sheet of markers, is hundreds of chunks of one wave); their positions a chunk earlier
             const int mbase = O0 + h + lane;
             Cand more, more2;
-            cand_at(pos_load(mbase), more);
+            cand_at(pos_load(mbase), src_load(mbase), more);
             int m = 0;
             if constexpr (PAIR) {
                 // two chunks set up before either's adds (two independent chains of
                 // set-up arithmetic per lane); their adds keep the chunk order.  The
                 // positions of a pair are loaded while the pair before it is added.
-                if (nmid > 1) cand_at(pos_load(mbase + SW), more2);
+                if (nmid > 1) cand_at(pos_load(mbase + SW), src_load(mbase + SW), more2);
                 int q2 = pos_load(mbase + SW * 2), q3 = pos_load(mbase + SW * 3);
+                int s2 = src_load(mbase + SW * 2), s3 = src_load(mbase + SW * 3);
                 for (; m + 1 < nmid; m += 2) {
                     const Cand n0 = more, n1 = more2;
-                    if (m + 2 < nmid) cand_at(q2, more);
-                    if (m + 3 < nmid) cand_at(q3, more2);
+                    if (m + 2 < nmid) cand_at(q2, s2, more);
+                    if (m + 3 < nmid) cand_at(q3, s3, more2);
                     q2 = pos_load(mbase + SW * (m + 4));
                     q3 = pos_load(mbase + SW * (m + 5));
+                    s2 = src_load(mbase + SW * (m + 4));
+                    s3 = src_load(mbase + SW * (m + 5));
                     process2(a, n0, n1);
                 }
             }
-            int q1 = pos_load(mbase + SW * (m + 1));
+            int q1 = pos_load(mbase + SW * (m + 1)), s1 = src_load(mbase + SW * (m + 1));
             for (; m < nmid; ++m) {
                 const Cand now = more;
-                if (m + 1 < nmid) cand_at(q1, more);
+                if (m + 1 < nmid) cand_at(q1, s1, more);
                 q1 = pos_load(mbase + SW * (m + 2));
+                s1 = src_load(mbase + SW * (m + 2));
                 process(a, 0, SW, now, nothing);
             }
         }
         if (a == alast && r_a > 0) {  // the last anchor's leftovers: stream O1 - r_a .. O1 - 1
             Cand last;
-            cand_at(pos_load(O1 - r_a + min(lane, r_a - 1)), last);
+            cand_at(pos_load(O1 - r_a + min(lane, r_a - 1)), src_load(O1 - r_a + min(lane, r_a - 1)), last);
             process(a, 0, r_a, last, nothing);
         }
         R0 = R1;
@@ -2676,7 +2718,7 @@ hipError_t launch_gather_F(const Params& p, hipStream_t s) {
 }
 template <int K>
 hipError_t launch_spread_sweep_t(const Params& p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, bool gather) {
-    if (gather)
+    if (gather && !p.cs_src)  // (cs_src: the sweep reads F at its row, no sorted_F)
         if (hipError_t e = launch_gather_F(p, s); e != hipSuccess) return e;
     if (ev0) (void)hipEventRecord(ev0, s);  // the events bracket the sweep kernels alone
     // One launch of every component.  Closed-form kernels run them all on the 5-slot
@@ -2691,13 +2733,18 @@ hipError_t launch_spread_sweep_t(const Params& p, hipStream_t s, hipEvent_t ev0,
         q.comp0 = 0;
         const dim3 g(sweep_grid(q, items)), b(SW);
         constexpr bool ZC = KT<K>::FAM == 0;
-        if (q.nadd) {
-            if (q.pd) hipLaunchKernelGGL((k_spread_sweep<K, true, true, ZC>), g, b, 0, s, q);
-            else hipLaunchKernelGGL((k_spread_sweep<K, false, true, ZC>), g, b, 0, s, q);
-        } else {
-            if (q.pd) hipLaunchKernelGGL((k_spread_sweep<K, true, false, ZC>), g, b, 0, s, q);
-            else hipLaunchKernelGGL((k_spread_sweep<K, false, false, ZC>), g, b, 0, s, q);
-        }
+        auto launch = [&](auto fs) {
+            constexpr bool FS = decltype(fs)::value;
+            if (q.nadd) {
+                if (q.pd) hipLaunchKernelGGL((k_spread_sweep<K, true, true, ZC, FS>), g, b, 0, s, q);
+                else hipLaunchKernelGGL((k_spread_sweep<K, false, true, ZC, FS>), g, b, 0, s, q);
+            } else {
+                if (q.pd) hipLaunchKernelGGL((k_spread_sweep<K, true, false, ZC, FS>), g, b, 0, s, q);
+                else hipLaunchKernelGGL((k_spread_sweep<K, false, false, ZC, FS>), g, b, 0, s, q);
+            }
+        };
+        if (q.cs_src) launch(std::true_type{});
+        else launch(std::false_type{});
     }
     if (ev1) (void)hipEventRecord(ev1, s);
     return hipGetLastError();
