@@ -129,6 +129,15 @@ _SIGS = [
     ("ibtk_le_forcegen_set_beams", c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("ibtk_le_forcegen_set_targets", c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("ibtk_le_forcegen_compute", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    ("ibtk_le_forcespecs_create", c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_void_p)]),
+    ("ibtk_le_forcespecs_destroy", c_int, [c_void_p]),
+    ("ibtk_le_forcespecs_set_springs", c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("ibtk_le_forcespecs_set_beams", c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("ibtk_le_forcespecs_set_targets", c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("ibtk_le_forcegen_renumber", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    ("ibtk_le_forcegen_renumber_stats", c_int, [c_void_p, ctypes.POINTER(ctypes.c_longlong)]),
+    ("ibtk_le_forcegen_plan_size", c_int, [c_void_p, c_int, ctypes.POINTER(ctypes.c_longlong)]),
+    ("ibtk_le_forcegen_plan_read", c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_longlong]),
     ("ibtk_le_slab_update_partition", c_int,
      [c_void_p, c_int, ctypes.c_longlong, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
       c_int, c_void_p, c_void_p]),

@@ -3123,6 +3123,16 @@ struct ibtk_le_forcegen_s {
     DevBuf soff, srec, boff, brec, toff, trec;
     long long ns = 0, nb = 0, nt = 0;  // springs, beams, target points in the plan
     bool need_U = false;               // some target point has eta != 0
+    bool valid = true;                 // false after a failed renumber, until a renumber or a set_* succeeds
+    // ibtk_le_forcegen_renumber: the inverse numbering, two key / value buffers for the
+    // sorts, the specs' deck indices in the new order, rocPRIM's scratch, the status record
+    DevBuf rn_perm, rn_k0, rn_k1, rn_v0, rn_v1, rn_dv, rn_temp, rn_st;
+    long long kept[3] = {0, 0, 0}, dropped[3] = {0, 0, 0};  // the last renumber's specs per class
+    long long n_alloc = 0;             // device allocations renumber has made for this plan
+    std::vector<DevBuf*> bufs() {
+        return {&soff, &srec, &boff, &brec, &toff, &trec, &rn_perm, &rn_k0, &rn_k1, &rn_v0, &rn_v1, &rn_dv, &rn_temp,
+                &rn_st};
+    }
 };
 
 extern "C" int ibtk_le_forcegen_create(ibtk_le_ctx ctx, int ndim, int n_nodes, ibtk_le_forcegen* out) {
@@ -3142,7 +3152,7 @@ extern "C" int ibtk_le_forcegen_destroy(ibtk_le_forcegen fg) {
     if (!fg) return IBTK_LE_OK;
     hipSetDevice(fg->ctx->device);
     hipStreamSynchronize(fg->ctx->stream);
-    for (DevBuf* b : {&fg->soff, &fg->srec, &fg->boff, &fg->brec, &fg->toff, &fg->trec}) b->release();
+    for (DevBuf* b : fg->bufs()) b->release();
     delete fg;
     return IBTK_LE_OK;
 }
@@ -3220,6 +3230,13 @@ int fg_set_targets(ibtk_le_forcegen fg, int n, const int* node, const double* ka
     }
     return fg_upload(fg, fg->toff, fg->trec, off, rec.data(), rec.size() * sizeof(FgTarget<ND>));
 }
+
+// a set_* that succeeded: the plan is usable again after a failed renumber (which left
+// every class empty)
+int fg_valid(ibtk_le_forcegen fg) {
+    fg->valid = true;
+    return IBTK_LE_OK;
+}
 }  // namespace
 
 extern "C" int ibtk_le_forcegen_set_springs(ibtk_le_forcegen fg, int n, const int* mastr, const int* slave,
@@ -3239,7 +3256,7 @@ extern "C" int ibtk_le_forcegen_set_springs(ibtk_le_forcegen fg, int n, const in
                         k, fcn_idx[k]);
     }
     fg->ns = 0;
-    if (n == 0) return IBTK_LE_OK;
+    if (n == 0) return fg_valid(fg);
     std::vector<int> cnt(fg->n, 0);
     for (int k = 0; k < n; ++k) {
         ++cnt[mastr[k]];
@@ -3255,7 +3272,7 @@ extern "C" int ibtk_le_forcegen_set_springs(ibtk_le_forcegen fg, int n, const in
     }
     if (int rc = fg_upload(fg, fg->soff, fg->srec, off, rec.data(), rec.size() * sizeof(FgSpring))) return rc;
     fg->ns = n;
-    return IBTK_LE_OK;
+    return fg_valid(fg);
 }
 
 extern "C" int ibtk_le_forcegen_set_beams(ibtk_le_forcegen fg, int n, const int* mastr, const int* next,
@@ -3271,12 +3288,12 @@ extern "C" int ibtk_le_forcegen_set_beams(ibtk_le_forcegen fg, int n, const int*
         if (mastr[k] == prev[k]) return fail(IBTK_LE_ERR_ARG, "beam %d: master and prev are both node %d", k, mastr[k]);
     }
     fg->nb = 0;
-    if (n == 0) return IBTK_LE_OK;
+    if (n == 0) return fg_valid(fg);
     const int rc = fg->ndim == 2 ? fg_set_beams<2>(fg, n, mastr, next, prev, bend, curv)
                                  : fg_set_beams<3>(fg, n, mastr, next, prev, bend, curv);
     if (rc) return rc;
     fg->nb = n;
-    return IBTK_LE_OK;
+    return fg_valid(fg);
 }
 
 extern "C" int ibtk_le_forcegen_set_targets(ibtk_le_forcegen fg, int n, const int* node, const double* kappa,
@@ -3288,13 +3305,13 @@ extern "C" int ibtk_le_forcegen_set_targets(ibtk_le_forcegen fg, int n, const in
         if (int rc = fg_node(fg, "target point", "its", k, node[k])) return rc;
     fg->nt = 0;
     fg->need_U = false;
-    if (n == 0) return IBTK_LE_OK;
+    if (n == 0) return fg_valid(fg);
     const int rc = fg->ndim == 2 ? fg_set_targets<2>(fg, n, node, kappa, eta, X0)
                                  : fg_set_targets<3>(fg, n, node, kappa, eta, X0);
     if (rc) return rc;
     fg->nt = n;
     for (int k = 0; eta && k < n; ++k) fg->need_U = fg->need_U || eta[k] != 0.0;
-    return IBTK_LE_OK;
+    return fg_valid(fg);
 }
 
 extern "C" int ibtk_le_forcegen_compute(ibtk_le_ctx ctx, ibtk_le_forcegen fg, const double* X_dev,
@@ -3304,6 +3321,8 @@ extern "C" int ibtk_le_forcegen_compute(ibtk_le_ctx ctx, ibtk_le_forcegen fg, co
     if (ctx->device != fg->ctx->device)
         return fail(IBTK_LE_ERR_ARG, "forcegen_compute: the plan lives on device %d, the context on %d", fg->ctx->device,
                     ctx->device);
+    if (!fg->valid)
+        return fail(IBTK_LE_ERR_ARG, "forcegen_compute: the plan is invalid: the last forcegen_renumber failed");
     if (fg->n == 0) return IBTK_LE_OK;
     if (!X_dev || !F_dev) return fail(IBTK_LE_ERR_ARG, "forcegen_compute: null array");
     if (fg->need_U && !U_dev)
@@ -3327,5 +3346,345 @@ extern "C" int ibtk_le_forcegen_compute(ibtk_le_ctx ctx, ibtk_le_forcegen fg, co
     p.F = F_dev;
     p.accumulate = accumulate ? 1 : 0;
     HIP_TRY(launch_forcegen(fg->ndim, p, ctx->stream));
+    return IBTK_LE_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The spec store (ibtk_le_forcespecs) and the plan rebuilt from it on the device when the
+// nodes are renumbered (ibtk_le_forcegen_renumber; the kernels are le_force_plan.hip's).
+// The store keeps the records of the plan in deck order with Lagrangian vertex indices;
+// it is uploaded once per structure set.  A renumbering then costs two radix sorts per
+// class and one small read of the status record, no upload.
+// ---------------------------------------------------------------------------
+struct ibtk_le_forcespecs_s {
+    ibtk_le_ctx ctx = nullptr;  // NULL: a host-only store, set_* validate and upload nothing
+    int ndim = 0, nv = 0;
+    DevBuf srec, brec, tnode, trec;  // FgSpring, FgBeam<ndim> (role 0), int, FgTarget<ndim>
+    int ns = 0, nb = 0, nt = 0;
+};
+
+extern "C" int ibtk_le_forcespecs_create(ibtk_le_ctx ctx, int ndim, int num_vertex, ibtk_le_forcespecs* out) {
+    if (!out) return fail(IBTK_LE_ERR_ARG, "forcespecs_create: null out");
+    if (ndim != 2 && ndim != 3) return fail(IBTK_LE_ERR_ARG, "forcespecs_create: ndim %d is not 2 or 3", ndim);
+    if (num_vertex < 0) return fail(IBTK_LE_ERR_ARG, "forcespecs_create: negative vertex count %d", num_vertex);
+    auto* fs = new ibtk_le_forcespecs_s();
+    fs->ctx = ctx;
+    fs->ndim = ndim;
+    fs->nv = num_vertex;
+    *out = fs;
+    return IBTK_LE_OK;
+}
+
+extern "C" int ibtk_le_forcespecs_destroy(ibtk_le_forcespecs fs) {
+    if (!fs) return IBTK_LE_OK;
+    if (fs->ctx) {
+        hipSetDevice(fs->ctx->device);
+        hipStreamSynchronize(fs->ctx->stream);
+        for (DevBuf* b : {&fs->srec, &fs->brec, &fs->tnode, &fs->trec}) b->release();
+    }
+    delete fs;
+    return IBTK_LE_OK;
+}
+
+namespace {
+int fs_vertex(ibtk_le_forcespecs fs, const char* what, const char* role, int k, int idx) {
+    if (idx < 0 || idx >= fs->nv)
+        return fail(IBTK_LE_ERR_ARG, "forcespecs: %s %d: %s vertex index %d is out of range [0, %d)", what, k, role, idx,
+                    fs->nv);
+    return IBTK_LE_OK;
+}
+
+// Replaces one array of the store (a blocking upload, once per structure set)
+int fs_upload(ibtk_le_forcespecs fs, DevBuf& d, const void* host, size_t bytes) {
+    if (!fs->ctx)
+        return fail(IBTK_LE_ERR_ARG, "forcespecs: the store was created without a context: nothing to upload to");
+    HIP_TRY(hipSetDevice(fs->ctx->device));
+    HIP_TRY(hipStreamSynchronize(fs->ctx->stream));
+    if (int rc = d.ensure(std::max<size_t>(bytes, 8))) return rc;
+    if (bytes) HIP_TRY(hipMemcpy(d.p, host, bytes, hipMemcpyHostToDevice));
+    return IBTK_LE_OK;
+}
+
+template <int ND>
+int fs_set_beams(ibtk_le_forcespecs fs, int n, const int* mastr, const int* next, const int* prev, const double* bend,
+                 const double* curv) {
+    std::vector<FgBeam<ND>> rec((size_t)n);
+    for (int k = 0; k < n; ++k) {
+        FgBeam<ND>& r = rec[(size_t)k];
+        r.m = mastr[k];
+        r.nx = next[k];
+        r.pv = prev[k];
+        r.role = 0;
+        r.bend = bend[k];
+        for (int d = 0; d < ND; ++d) r.curv[d] = curv ? curv[(size_t)k * ND + d] : 0.0;
+    }
+    return fs_upload(fs, fs->brec, rec.data(), rec.size() * sizeof(FgBeam<ND>));
+}
+
+template <int ND>
+int fs_set_targets(ibtk_le_forcespecs fs, int n, const int* node, const double* kappa, const double* eta,
+                   const double* X0) {
+    std::vector<FgTarget<ND>> rec((size_t)n);
+    for (int k = 0; k < n; ++k) {
+        FgTarget<ND>& r = rec[(size_t)k];
+        r.kappa = kappa[k];
+        r.eta = eta ? eta[k] : 0.0;
+        for (int d = 0; d < ND; ++d) r.X0[d] = X0[(size_t)k * ND + d];
+    }
+    if (int rc = fs_upload(fs, fs->tnode, node, (size_t)n * sizeof(int))) return rc;
+    return fs_upload(fs, fs->trec, rec.data(), rec.size() * sizeof(FgTarget<ND>));
+}
+}  // namespace
+
+extern "C" int ibtk_le_forcespecs_set_springs(ibtk_le_forcespecs fs, int n, const int* mastr, const int* slave,
+                                              const double* kappa, const double* rest, const int* fcn_idx) {
+    if (!fs) return fail(IBTK_LE_ERR_ARG, "forcespecs_set_springs: null spec store");
+    if (n < 0) return fail(IBTK_LE_ERR_ARG, "forcespecs_set_springs: negative spring count %d", n);
+    if (n > 0 && (!mastr || !slave || !kappa || !rest))
+        return fail(IBTK_LE_ERR_ARG, "forcespecs_set_springs: null array");
+    for (int k = 0; k < n; ++k) {
+        if (int rc = fs_vertex(fs, "spring", "master", k, mastr[k])) return rc;
+        if (int rc = fs_vertex(fs, "spring", "slave", k, slave[k])) return rc;
+        if (mastr[k] == slave[k])
+            return fail(IBTK_LE_ERR_ARG, "forcespecs: spring %d: master and slave are both vertex %d", k, mastr[k]);
+        if (fcn_idx && fcn_idx[k] != 0)
+            return fail(IBTK_LE_ERR_ARG,
+                        "forcespecs: spring %d: force function index %d: only the default Hookean law (index 0) runs "
+                        "on the device",
+                        k, fcn_idx[k]);
+    }
+    if (n == 0) {
+        fs->ns = 0;
+        return IBTK_LE_OK;
+    }
+    std::vector<FgSpring> rec((size_t)n);
+    for (int k = 0; k < n; ++k) rec[(size_t)k] = FgSpring{mastr[k], slave[k], kappa[k], rest[k]};
+    fs->ns = 0;
+    if (int rc = fs_upload(fs, fs->srec, rec.data(), rec.size() * sizeof(FgSpring))) return rc;
+    fs->ns = n;
+    return IBTK_LE_OK;
+}
+
+extern "C" int ibtk_le_forcespecs_set_beams(ibtk_le_forcespecs fs, int n, const int* mastr, const int* next,
+                                            const int* prev, const double* bend, const double* curv) {
+    if (!fs) return fail(IBTK_LE_ERR_ARG, "forcespecs_set_beams: null spec store");
+    if (n < 0) return fail(IBTK_LE_ERR_ARG, "forcespecs_set_beams: negative beam count %d", n);
+    if (n > 0 && (!mastr || !next || !prev || !bend)) return fail(IBTK_LE_ERR_ARG, "forcespecs_set_beams: null array");
+    for (int k = 0; k < n; ++k) {
+        if (int rc = fs_vertex(fs, "beam", "master", k, mastr[k])) return rc;
+        if (int rc = fs_vertex(fs, "beam", "next", k, next[k])) return rc;
+        if (int rc = fs_vertex(fs, "beam", "prev", k, prev[k])) return rc;
+        if (mastr[k] == next[k])
+            return fail(IBTK_LE_ERR_ARG, "forcespecs: beam %d: master and next are both vertex %d", k, mastr[k]);
+        if (mastr[k] == prev[k])
+            return fail(IBTK_LE_ERR_ARG, "forcespecs: beam %d: master and prev are both vertex %d", k, mastr[k]);
+    }
+    if (n == 0) {
+        fs->nb = 0;
+        return IBTK_LE_OK;
+    }
+    fs->nb = 0;
+    const int rc = fs->ndim == 2 ? fs_set_beams<2>(fs, n, mastr, next, prev, bend, curv)
+                                 : fs_set_beams<3>(fs, n, mastr, next, prev, bend, curv);
+    if (rc) return rc;
+    fs->nb = n;
+    return IBTK_LE_OK;
+}
+
+extern "C" int ibtk_le_forcespecs_set_targets(ibtk_le_forcespecs fs, int n, const int* node, const double* kappa,
+                                              const double* eta, const double* X0) {
+    if (!fs) return fail(IBTK_LE_ERR_ARG, "forcespecs_set_targets: null spec store");
+    if (n < 0) return fail(IBTK_LE_ERR_ARG, "forcespecs_set_targets: negative target point count %d", n);
+    if (n > 0 && (!node || !kappa || !X0)) return fail(IBTK_LE_ERR_ARG, "forcespecs_set_targets: null array");
+    for (int k = 0; k < n; ++k)
+        if (int rc = fs_vertex(fs, "target point", "its", k, node[k])) return rc;
+    if (n == 0) {
+        fs->nt = 0;
+        return IBTK_LE_OK;
+    }
+    fs->nt = 0;
+    const int rc = fs->ndim == 2 ? fs_set_targets<2>(fs, n, node, kappa, eta, X0)
+                                 : fs_set_targets<3>(fs, n, node, kappa, eta, X0);
+    if (rc) return rc;
+    fs->nt = n;
+    return IBTK_LE_OK;
+}
+
+namespace {
+// A renumber buffer at least `bytes` long.  Growing frees the old block: anything enqueued
+// that still reads it finishes first, as fg_upload waits before it replaces a plan.
+int fg_grow(ibtk_le_forcegen fg, hipStream_t s, DevBuf& b, size_t bytes) {
+    if (bytes <= b.cap) return IBTK_LE_OK;
+    HIP_TRY(hipStreamSynchronize(s));
+    if (fg->ctx->stream != s) HIP_TRY(hipStreamSynchronize(fg->ctx->stream));
+    ++fg->n_alloc;
+    return b.ensure(bytes);
+}
+
+int fg_sort(ibtk_le_forcegen fg, hipStream_t s, const unsigned* kin, unsigned* kout, const int* vin, int* vout, int n,
+            int bits) {
+    size_t tb = 0;
+    HIP_TRY(launch_sort(nullptr, tb, kin, kout, vin, vout, n, bits, s));
+    if (int rc = fg_grow(fg, s, fg->rn_temp, std::max<size_t>(tb, 8))) return rc;
+    tb = fg->rn_temp.cap;
+    HIP_TRY(launch_sort(fg->rn_temp.p, tb, kin, kout, vin, vout, n, bits, s));
+    return IBTK_LE_OK;
+}
+
+size_t fg_rec_bytes(int ndim, int cls) {
+    if (cls == 0) return sizeof(FgSpring);
+    if (cls == 1) return ndim == 2 ? sizeof(FgBeam<2>) : sizeof(FgBeam<3>);
+    return ndim == 2 ? sizeof(FgTarget<2>) : sizeof(FgTarget<3>);
+}
+
+// the device work of a renumber: everything up to the read of the status record
+int fg_renumber_device(ibtk_le_ctx ctx, ibtk_le_forcegen fg, ibtk_le_forcespecs fs, const int* order_dev, int n_order,
+                       FpStatus& h) {
+    hipStream_t s = ctx->stream;
+    const int nd = fg->ndim, n = fg->n;
+    const int cnt[3] = {fs->ns, fs->nb, fs->nt};
+    const long long E[3] = {2LL * fs->ns, 3LL * fs->nb, (long long)fs->nt};
+    const size_t emax = (size_t)std::max<long long>(1, std::max(E[0], std::max(E[1], E[2])));
+    DevBuf* off[3] = {&fg->soff, &fg->boff, &fg->toff};
+    DevBuf* rec[3] = {&fg->srec, &fg->brec, &fg->trec};
+    const void* store[3] = {fs->srec.p, fs->brec.p, fs->trec.p};
+    // every size comes from the store's totals, not from what this numbering keeps: a later
+    // renumber with the same store allocates nothing
+    if (int rc = fg_grow(fg, s, fg->rn_st, sizeof(FpStatus))) return rc;
+    if (int rc = fg_grow(fg, s, fg->rn_perm, sizeof(int) * (size_t)std::max(fs->nv, 1))) return rc;
+    for (DevBuf* b : {&fg->rn_k0, &fg->rn_k1, &fg->rn_v0, &fg->rn_v1})
+        if (int rc = fg_grow(fg, s, *b, 4 * emax)) return rc;
+    if (int rc = fg_grow(fg, s, fg->rn_dv, sizeof(int) * (size_t)std::max(1, std::max(fs->ns, fs->nb)))) return rc;
+    for (int c = 0; c < 3; ++c) {
+        if (!cnt[c]) continue;
+        if (int rc = fg_grow(fg, s, *off[c], sizeof(long long) * ((size_t)n + 1))) return rc;
+        if (int rc = fg_grow(fg, s, *rec[c], (size_t)E[c] * fg_rec_bytes(nd, c))) return rc;
+    }
+    int bits = 1;  // the keys are node indices and the sentinel n: at least one bit (n = 1)
+    while (bits < 32 && (1ULL << bits) <= (unsigned long long)n) ++bits;
+    const unsigned sentinel = (unsigned)n;
+    int* perm = fg->rn_perm.as<int>();
+    FpStatus* st = fg->rn_st.as<FpStatus>();
+    unsigned *k0 = fg->rn_k0.as<unsigned>(), *k1 = fg->rn_k1.as<unsigned>();
+    int *v0 = fg->rn_v0.as<int>(), *v1 = fg->rn_v1.as<int>(), *dv = fg->rn_dv.as<int>();
+    HIP_TRY(launch_fp_perm(order_dev, n_order, fs->nv, perm, st, s));
+    for (int c = 0; c < 2; ++c) {
+        if (!cnt[c]) continue;
+        const int e = (int)E[c];
+        HIP_TRY(launch_fp_deck_keys(c, nd, store[c], cnt[c], perm, sentinel, k0, v0, st, s));
+        if (int rc = fg_sort(fg, s, k0, k1, v0, dv, cnt[c], bits)) return rc;
+        HIP_TRY(launch_fp_entries(c, nd, store[c], cnt[c], dv, perm, sentinel, k0, v0, s));
+        if (int rc = fg_sort(fg, s, k0, k1, v0, v1, e, bits)) return rc;
+        HIP_TRY(launch_fp_offsets(c, k1, e, n, off[c]->as<long long>(), st, s));
+        HIP_TRY(launch_fp_gather(c, nd, k1, v1, e, sentinel, dv, store[c], perm, rec[c]->p, s));
+    }
+    if (cnt[2]) {
+        HIP_TRY(launch_fp_target_keys(nd, fs->tnode.as<int>(), store[2], cnt[2], perm, sentinel, k0, v0, st, s));
+        if (int rc = fg_sort(fg, s, k0, k1, v0, v1, cnt[2], bits)) return rc;
+        HIP_TRY(launch_fp_offsets(2, k1, cnt[2], n, off[2]->as<long long>(), st, s));
+        HIP_TRY(launch_fp_gather(2, nd, k1, v1, cnt[2], sentinel, nullptr, store[2], perm, rec[2]->p, s));
+    }
+    HIP_TRY(hipMemcpyAsync(&h, st, sizeof(FpStatus), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return IBTK_LE_OK;
+}
+}  // namespace
+
+extern "C" int ibtk_le_forcegen_renumber(ibtk_le_ctx ctx, ibtk_le_forcegen fg, ibtk_le_forcespecs fs,
+                                         const int* order_dev, int n_order) {
+    if (!ctx) return fail(IBTK_LE_ERR_ARG, "forcegen_renumber: null context");
+    if (!fg) return fail(IBTK_LE_ERR_ARG, "forcegen_renumber: null force generator");
+    if (!fs) return fail(IBTK_LE_ERR_ARG, "forcegen_renumber: null spec store");
+    if (!fs->ctx) return fail(IBTK_LE_ERR_ARG, "forcegen_renumber: the spec store was created without a context");
+    if (ctx->device != fg->ctx->device || ctx->device != fs->ctx->device)
+        return fail(IBTK_LE_ERR_ARG, "forcegen_renumber: the context, the plan and the spec store live on devices %d, %d, %d",
+                    ctx->device, fg->ctx->device, fs->ctx->device);
+    if (fg->ndim != fs->ndim)
+        return fail(IBTK_LE_ERR_ARG, "forcegen_renumber: the plan has ndim %d, the spec store %d", fg->ndim, fs->ndim);
+    if (n_order < 0 || n_order > fg->n)
+        return fail(IBTK_LE_ERR_ARG, "forcegen_renumber: n_order %d is outside [0, %d], the plan's nodes", n_order, fg->n);
+    if (n_order > 0 && !order_dev) return fail(IBTK_LE_ERR_ARG, "forcegen_renumber: null order");
+    if (2LL * fs->ns > INT_MAX || 3LL * fs->nb > INT_MAX)
+        return fail(IBTK_LE_ERR_RANGE, "forcegen_renumber: %lld spring or %lld beam entries exceed 2^31 - 1",
+                    2LL * fs->ns, 3LL * fs->nb);
+    const long long total[3] = {fs->ns, fs->nb, fs->nt};
+    // from here on the old plan is gone, whatever happens
+    fg->ns = fg->nb = fg->nt = 0;
+    fg->need_U = false;
+    for (int c = 0; c < 3; ++c) {
+        fg->kept[c] = 0;
+        fg->dropped[c] = total[c];
+    }
+    if (n_order == 0 || (!fs->ns && !fs->nb && !fs->nt)) return fg_valid(fg);  // nothing kept: no launch
+    fg->valid = false;
+    HIP_TRY(hipSetDevice(ctx->device));
+    FpStatus h{};
+    if (int rc = fg_renumber_device(ctx, fg, fs, order_dev, n_order, h)) return rc;
+    if (h.bad_order != INT_MAX)
+        return fail(IBTK_LE_ERR_ARG, "forcegen_renumber: order[%d] is outside [0, %d), the store's vertices",
+                    h.bad_order, fs->nv);
+    if (h.dup_lag != INT_MAX)
+        return fail(IBTK_LE_ERR_ARG, "forcegen_renumber: order names Lagrangian index %d more than once", h.dup_lag);
+    if (h.bad_spec[0] != INT_MAX)
+        return fail(IBTK_LE_ERR_ARG,
+                    "forcegen_renumber: spring %d of the deck is kept (its master is in order) but its slave is absent",
+                    h.bad_spec[0]);
+    if (h.bad_spec[1] != INT_MAX)
+        return fail(IBTK_LE_ERR_ARG,
+                    "forcegen_renumber: beam %d of the deck is kept (its master is in order) but its next or prev "
+                    "vertex is absent",
+                    h.bad_spec[1]);
+    fg->ns = h.kept[0];
+    fg->nb = h.kept[1];
+    fg->nt = h.kept[2];
+    fg->need_U = h.need_U != 0;
+    for (int c = 0; c < 3; ++c) {
+        fg->kept[c] = h.kept[c];
+        fg->dropped[c] = total[c] - h.kept[c];
+    }
+    return fg_valid(fg);
+}
+
+extern "C" int ibtk_le_forcegen_renumber_stats(ibtk_le_forcegen fg, long long* out) {
+    if (!fg || !out) return fail(IBTK_LE_ERR_ARG, "forcegen_renumber_stats: null argument");
+    for (int c = 0; c < 3; ++c) {
+        out[c] = fg->kept[c];
+        out[3 + c] = fg->dropped[c];
+    }
+    size_t bytes = 0;
+    for (DevBuf* b : fg->bufs()) bytes += b->cap;
+    out[6] = (long long)bytes;
+    out[7] = fg->n_alloc;
+    return IBTK_LE_OK;
+}
+
+extern "C" int ibtk_le_forcegen_plan_size(ibtk_le_forcegen fg, int cls, long long* n_entries) {
+    if (!fg || !n_entries) return fail(IBTK_LE_ERR_ARG, "forcegen_plan_size: null argument");
+    if (cls < 0 || cls > 2) return fail(IBTK_LE_ERR_ARG, "forcegen_plan_size: class %d is not 0, 1 or 2", cls);
+    if (!fg->valid) return fail(IBTK_LE_ERR_ARG, "forcegen_plan_size: the plan is invalid: the last forcegen_renumber failed");
+    *n_entries = cls == 0 ? 2 * fg->ns : cls == 1 ? 3 * fg->nb : fg->nt;
+    return IBTK_LE_OK;
+}
+
+extern "C" int ibtk_le_forcegen_plan_read(ibtk_le_forcegen fg, int cls, long long* off_host, void* rec_host,
+                                          long long rec_bytes) {
+    long long ne = 0;
+    if (int rc = ibtk_le_forcegen_plan_size(fg, cls, &ne)) return rc;
+    if (!off_host) return fail(IBTK_LE_ERR_ARG, "forcegen_plan_read: null offsets");
+    const long long want = ne * (long long)fg_rec_bytes(fg->ndim, cls);
+    if (rec_bytes != want)
+        return fail(IBTK_LE_ERR_ARG, "forcegen_plan_read: rec_bytes %lld, the class holds %lld entries of %zu bytes",
+                    rec_bytes, ne, fg_rec_bytes(fg->ndim, cls));
+    if (ne > 0 && !rec_host) return fail(IBTK_LE_ERR_ARG, "forcegen_plan_read: null records");
+    if (ne == 0) {  // an empty class has no device arrays
+        for (long long i = 0; i <= fg->n; ++i) off_host[i] = 0;
+        return IBTK_LE_OK;
+    }
+    const DevBuf& off = cls == 0 ? fg->soff : cls == 1 ? fg->boff : fg->toff;
+    const DevBuf& rec = cls == 0 ? fg->srec : cls == 1 ? fg->brec : fg->trec;
+    HIP_TRY(hipSetDevice(fg->ctx->device));
+    HIP_TRY(hipStreamSynchronize(fg->ctx->stream));
+    HIP_TRY(hipMemcpy(off_host, off.p, sizeof(long long) * ((size_t)fg->n + 1), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rec_host, rec.p, (size_t)want, hipMemcpyDeviceToHost));
     return IBTK_LE_OK;
 }

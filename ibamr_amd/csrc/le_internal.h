@@ -328,6 +328,33 @@ struct ForceGenParams {
     int accumulate;                        // F = F + acc, else F = acc
 };
 hipError_t launch_forcegen(int ndim, const ForceGenParams& p, hipStream_t s);
+// The plan rebuilt on the device for a new numbering (le_force_plan.hip,
+// ibtk_le_forcegen_renumber).  The spec store holds the same records in deck order with
+// Lagrangian vertex indices (beams with role 0; target points beside an int array of their
+// vertices).  cls: 0 springs, 1 beams, 2 target points.  The status record: INT_MAX = none.
+struct FpStatus {
+    int bad_order;    // first order entry outside [0, num_vertex)
+    int dup_lag;      // smallest Lagrangian index that order names twice
+    int bad_spec[3];  // per class: first deck spec that is kept and has an absent endpoint
+    int kept[3];      // per class: specs in the plan
+    int need_U;       // a kept target point has eta != 0
+};
+// perm[0:nv] = -1, the status cleared, then perm[order[i]] = i for the entries in range
+hipError_t launch_fp_perm(const int* order, int n_order, int nv, int* perm, FpStatus* st, hipStream_t s);
+// keys[j] = perm[master of deck spec j], or sentinel (dropped, or flagged); vals[j] = j
+hipError_t launch_fp_deck_keys(int cls, int ndim, const void* rec, int n, const int* perm, unsigned sentinel,
+                               unsigned* keys, int* vals, FpStatus* st, hipStream_t s);
+hipError_t launch_fp_target_keys(int ndim, const int* node, const void* rec, int n, const int* perm,
+                                 unsigned sentinel, unsigned* keys, int* vals, FpStatus* st, hipStream_t s);
+// spec k = deck spec dv[k]: entries R k + role (R = 2 springs, 3 beams) keyed by their nodes
+hipError_t launch_fp_entries(int cls, int ndim, const void* rec, int n, const int* dv, const int* perm,
+                             unsigned sentinel, unsigned* ekeys, int* evals, hipStream_t s);
+// off[i] = first of the E sorted entries keyed >= i, i = 0 .. n_nodes; st->kept[cls]
+hipError_t launch_fp_offsets(int cls, const unsigned* skeys, int E, int n_nodes, long long* off, FpStatus* st,
+                             hipStream_t s);
+// out[p] = the record of sorted entry p (keys below sentinel), node indices through perm
+hipError_t launch_fp_gather(int cls, int ndim, const unsigned* skeys, const int* svals, int E, unsigned sentinel,
+                            const int* dv, const void* rec, const int* perm, void* out, hipStream_t s);
 hipError_t launch_gather_col(int kernel, const Params& p, int n, int* sorted_s, double* sorted_X,
                              const unsigned* sorted_key, int nbuckets, int* bucket_start, hipStream_t s);
 hipError_t launch_interp_sweep(int kernel, const Params& p, int n, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);

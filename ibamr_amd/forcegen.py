@@ -2,7 +2,7 @@
 
 ``IBStandardForceGen::computeLagrangianForce`` (``src/IB/IBStandardForceGen.cpp:265-313``)
 produces the ``F`` that ``spread`` consumes, from ``X`` and ``U``, every step between the
-position update and the spread.  Two pieces live here:
+position update and the spread.  Three pieces live here:
 
 * :class:`ForceSpecs` -- the host side.  It holds what the deck readers of
   :mod:`ibamr_amd.io` return for one or more structures and flattens it into the arrays
@@ -14,6 +14,10 @@ position update and the spread.  Two pieces live here:
 * :class:`ForceGen` -- the device plan built through the C ABI
   (``ibtk_le_forcegen_*``) and its ``compute``: one gather kernel, a lane per node,
   the serial loops' result bit for bit, no host synchronisation.
+
+* :class:`DeviceForceSpecs` -- the specs on the device in Lagrangian indices
+  (``ibtk_le_forcespecs``), from which :meth:`ForceGen.renumber` rebuilds the plan on the
+  device whenever a regrid renumbers the nodes.
 """
 from __future__ import annotations
 
@@ -27,7 +31,7 @@ import numpy as np
 from . import _lib, io
 from ._lib import check
 
-__all__ = ["SpringArrays", "BeamArrays", "TargetArrays", "ForceSpecs", "ForceGen"]
+__all__ = ["SpringArrays", "BeamArrays", "TargetArrays", "ForceSpecs", "ForceGen", "DeviceForceSpecs"]
 
 
 class SpringArrays(NamedTuple):
@@ -169,28 +173,57 @@ class ForceSpecs:
             perm = np.asarray(perm, dtype=np.int64).reshape(-1)
             if perm.size != nv:
                 raise ValueError(f"perm has {perm.size} entries, the structures {nv} vertices")
+        lag = self.lagrangian_arrays()
+        out = {"springs": None, "beams": None, "targets": None}
+        if lag["springs"] is not None:
+            s = lag["springs"]
+            o = np.argsort(perm[s.mastr], kind="stable")
+            out["springs"] = SpringArrays(_i32(perm[s.mastr][o]), _i32(perm[s.slave][o]), s.kappa[o].copy(),
+                                          s.rest[o].copy(), _i32(s.fcn_idx[o]))
+        if lag["beams"] is not None:
+            b = lag["beams"]
+            o = np.argsort(perm[b.mastr], kind="stable")
+            out["beams"] = BeamArrays(_i32(perm[b.mastr][o]), _i32(perm[b.next][o]), _i32(perm[b.prev][o]),
+                                      b.bend[o].copy(), _f64(b.curv[o], (-1, self.ndim)))
+        if lag["targets"] is not None:
+            t = lag["targets"]
+            o = np.argsort(perm[t.node], kind="stable")
+            out["targets"] = TargetArrays(_i32(perm[t.node][o]), t.kappa[o].copy(), t.eta[o].copy(),
+                                          _f64(t.X0[o], (-1, self.ndim)))
+        return out
+
+    def lagrangian_arrays(self) -> dict:
+        """What :meth:`arrays` settles before the numbering comes in: the same dictionary of
+        ``SpringArrays`` / ``BeamArrays`` / ``TargetArrays`` (or None), in **deck order** with
+        **Lagrangian vertex indices**.
+
+        * A spring's master is the smaller Lagrangian index of its edge.
+        * Every line of a repeated edge has the parameters of the edge's first line.
+        * A target point carries ``X0[node]``.
+
+        This is what the device spec store (:class:`DeviceForceSpecs`) uploads once;
+        ``arrays(perm)`` is its stable sort by ``perm[master]`` with every index taken
+        through ``perm``.
+        """
         out = {"springs": None, "beams": None, "targets": None}
         if self.springs is not None:
             s = self.springs
             m = np.minimum(s.mastr, s.slave).astype(np.int64)
             v = np.maximum(s.mastr, s.slave).astype(np.int64)
-            first: dict = {}
-            src = np.empty(m.size, dtype=np.int64)
-            for k, e in enumerate(zip(m.tolist(), v.tolist())):
-                src[k] = first.setdefault(e, k)
-            o = np.argsort(perm[m], kind="stable")
-            out["springs"] = SpringArrays(_i32(perm[m][o]), _i32(perm[v][o]), s.kappa[src][o].copy(),
-                                          s.rest[src][o].copy(), _i32(s.fcn_idx[src][o]))
+            # src[k]: the first line of k's edge (np.unique's index is the first occurrence)
+            _, first, inv = np.unique(m * (max(self.num_vertex, int(v.max(initial=0)) + 1)) + v, return_index=True,
+                                      return_inverse=True)
+            src = first[inv.reshape(-1)]
+            out["springs"] = SpringArrays(_i32(m), _i32(v), s.kappa[src].copy(), s.rest[src].copy(),
+                                          _i32(s.fcn_idx[src]))
         if self.beams is not None:
             b = self.beams
-            o = np.argsort(perm[b.mastr.astype(np.int64)], kind="stable")
-            out["beams"] = BeamArrays(_i32(perm[b.mastr][o]), _i32(perm[b.next][o]), _i32(perm[b.prev][o]),
-                                      b.bend[o].copy(), _f64(b.curv[o], (-1, self.ndim)))
+            out["beams"] = BeamArrays(_i32(b.mastr), _i32(b.next), _i32(b.prev), b.bend.copy(),
+                                      _f64(b.curv, (-1, self.ndim)))
         if self.targets is not None:
             t = self.targets
-            o = np.argsort(perm[t.node.astype(np.int64)], kind="stable")
-            out["targets"] = TargetArrays(_i32(perm[t.node][o]), t.kappa[o].copy(), t.eta[o].copy(),
-                                          _f64(self.X0[t.node[o]], (-1, self.ndim)))
+            out["targets"] = TargetArrays(_i32(t.node), t.kappa.copy(), t.eta.copy(),
+                                          _f64(self.X0[t.node], (-1, self.ndim)))
         return out
 
 
@@ -272,9 +305,102 @@ class ForceGen:
                                                 int(bool(accumulate))))
         return F
 
+    def renumber(self, dspecs: "DeviceForceSpecs", order) -> dict:
+        """Replace the whole plan with the one of the numbering ``order`` -- an int32 device
+        tensor, ``order[i]`` the Lagrangian index of node ``i`` (what ``le.node_distribution``
+        returns), at most ``n_nodes`` long -- built on the device from the spec store
+        ``dspecs``: byte for byte the plan ``from_specs(ctx, specs, perm=inverse(order))``
+        uploads.  A spec whose master is not in ``order`` is dropped; a kept spec with an
+        absent endpoint, an ``order`` entry out of range or a repeated one raise
+        ``IBTKLEError`` (ARG) and leave the plan invalid (``compute`` raises) until a
+        ``renumber`` or a ``set_*`` succeeds.  Blocks for one small read.  Returns
+        :meth:`renumber_stats`."""
+        import torch
+
+        from .le import _ptr
+        if order.dtype != torch.int32 or order.dim() != 1 or not order.is_contiguous():
+            raise ValueError("order must be a contiguous 1-D int32 device tensor")
+        check(self.lib.ibtk_le_forcegen_renumber(self.ctx.h, self.h, dspecs.h, _ptr(order), int(order.numel())))
+        return self.renumber_stats()
+
+    def renumber_stats(self) -> dict:
+        """The last :meth:`renumber`: specs ``kept`` and ``dropped`` per class (springs, beams,
+        target points), the device ``bytes`` the plan and its scratch hold, and the device
+        ``allocations`` the renumber calls have made so far."""
+        out = (ctypes.c_longlong * 8)()
+        check(self.lib.ibtk_le_forcegen_renumber_stats(self.h, out))
+        return {"kept": tuple(out[0:3]), "dropped": tuple(out[3:6]), "bytes": out[6], "allocations": out[7]}
+
+    def record_dtype(self, cls: int) -> np.dtype:
+        """The structured dtype of class ``cls``'s plan records (0 springs, 1 beams, 2 target
+        points); no padding."""
+        nd = self.ndim
+        return np.dtype([
+            [("m", "<i4"), ("s", "<i4"), ("kappa", "<f8"), ("rest", "<f8")],
+            [("m", "<i4"), ("next", "<i4"), ("prev", "<i4"), ("role", "<i4"), ("bend", "<f8"), ("curv", "<f8", (nd,))],
+            [("kappa", "<f8"), ("eta", "<f8"), ("X0", "<f8", (nd,))],
+        ][cls])
+
+    def plan(self, cls: int):
+        """The plan of class ``cls`` read back (blocking; tests and debugging):
+        ``(offsets, records)``, ``n_nodes + 1`` int64 row offsets and a structured array of
+        the entries (:meth:`record_dtype`)."""
+        ne = ctypes.c_longlong()
+        check(self.lib.ibtk_le_forcegen_plan_size(self.h, int(cls), ctypes.byref(ne)))
+        off = np.empty(self.n_nodes + 1, dtype=np.int64)
+        rec = np.empty(ne.value, dtype=self.record_dtype(cls))
+        check(self.lib.ibtk_le_forcegen_plan_read(self.h, int(cls), _host_ptr(off), _host_ptr(rec), rec.nbytes))
+        return off, rec
+
     def close(self):
         if getattr(self, "h", None) and getattr(self.ctx, "h", None):
             self.lib.ibtk_le_forcegen_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        if sys.is_finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceForceSpecs:
+    """The specs of a :class:`ForceSpecs` on the device, in Lagrangian vertex indices and
+    deck order (``ibtk_le_forcespecs``): uploaded here, once per structure set, and then the
+    source of every :meth:`ForceGen.renumber`.  ``specs.lagrangian_arrays()`` is what goes
+    up; the library validates it on the host first."""
+
+    def __init__(self, ctx, specs: ForceSpecs):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        self.ndim = specs.ndim
+        self.num_vertex = specs.num_vertex
+        h = ctypes.c_void_p()
+        check(self.lib.ibtk_le_forcespecs_create(ctx.h, self.ndim, self.num_vertex, ctypes.byref(h)))
+        self.h = h
+        a = specs.lagrangian_arrays()
+        self.counts = tuple(0 if a[c] is None else int(a[c][0].size) for c in ("springs", "beams", "targets"))
+        if a["springs"] is not None:
+            s = a["springs"]
+            check(self.lib.ibtk_le_forcespecs_set_springs(self.h, s.mastr.size, _host_ptr(s.mastr), _host_ptr(s.slave),
+                                                          _host_ptr(_f64(s.kappa, (-1,))), _host_ptr(_f64(s.rest, (-1,))),
+                                                          _host_ptr(s.fcn_idx)))
+        if a["beams"] is not None:
+            b = a["beams"]
+            check(self.lib.ibtk_le_forcespecs_set_beams(self.h, b.mastr.size, _host_ptr(b.mastr), _host_ptr(b.next),
+                                                        _host_ptr(b.prev), _host_ptr(_f64(b.bend, (-1,))),
+                                                        _host_ptr(b.curv)))
+        if a["targets"] is not None:
+            t = a["targets"]
+            check(self.lib.ibtk_le_forcespecs_set_targets(self.h, t.node.size, _host_ptr(t.node),
+                                                          _host_ptr(_f64(t.kappa, (-1,))), _host_ptr(_f64(t.eta, (-1,))),
+                                                          _host_ptr(t.X0)))
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.lib.ibtk_le_forcespecs_destroy(self.h)
         self.h = None
 
     def __del__(self):

@@ -560,6 +560,81 @@ int ibtk_le_forcegen_set_targets(ibtk_le_forcegen fg, int n, const int* node, co
 int ibtk_le_forcegen_compute(ibtk_le_ctx ctx, ibtk_le_forcegen fg, const double* X_dev, const double* dX_dev,
                              const double* U_dev, double* F_dev, int accumulate);
 
+/* ---- The force plan rebuilt on the device when the nodes are renumbered ---------------
+ * LDataManager::endDataRedistribution gives the nodes new local indices at every regrid;
+ * the reference then runs IBStandardForceGen::initializeLevelData again, which renumbers
+ * the specs ("master by master in local node order, deck order within a master") and so
+ * changes every node's summation order.  ibtk_le_forcegen_set_* would rebuild the plan on
+ * the host and upload it; the calls below keep the specs on the device in LAGRANGIAN
+ * vertex indices and deck order (uploaded once per structure set) and rebuild the plan
+ * from them with device work alone.
+ *
+ * ibtk_le_forcespecs: the store, over num_vertex Lagrangian vertices.  The set_* calls
+ * take HOST arrays in deck order with what does not depend on the numbering settled by
+ * the caller: a spring's master is its smaller Lagrangian index and a repeated edge has
+ * the parameters of its first line on every line (IBStandardInitializer.cpp:979-987,
+ * 2848; ibamr_amd.forcegen.ForceSpecs.lagrangian_arrays does both); a target point
+ * carries its anchor X0[k][ndim] inline.  They validate on the host before any device
+ * call (IBTK_LE_ERR_ARG with a message: a NULL store, a negative count, a NULL array with
+ * n > 0, an index outside [0, num_vertex), mastr == slave / next / prev, fcn_idx != 0)
+ * and then replace that class of the store with a blocking upload (n = 0 clears it).
+ * fcn_idx, curv and eta may be NULL.  ctx may be NULL: such a store only validates -- a
+ * set_* with valid arguments and n > 0 then returns IBTK_LE_ERR_ARG ("without a
+ * context") -- and cannot be renumbered from. */
+typedef struct ibtk_le_forcespecs_s* ibtk_le_forcespecs;
+int ibtk_le_forcespecs_create(ibtk_le_ctx ctx, int ndim, int num_vertex, ibtk_le_forcespecs* out);
+int ibtk_le_forcespecs_destroy(ibtk_le_forcespecs fs);
+int ibtk_le_forcespecs_set_springs(ibtk_le_forcespecs fs, int n, const int* mastr, const int* slave,
+                                   const double* kappa, const double* rest, const int* fcn_idx);
+int ibtk_le_forcespecs_set_beams(ibtk_le_forcespecs fs, int n, const int* mastr, const int* next, const int* prev,
+                                 const double* bend, const double* curv);
+int ibtk_le_forcespecs_set_targets(ibtk_le_forcespecs fs, int n, const int* node, const double* kappa,
+                                   const double* eta, const double* X0);
+/* Replaces all three classes of fg's plan with the plan of the numbering order_dev:
+ * order_dev[i] (device, n_order <= n_nodes ints) is the Lagrangian index of node i --
+ * what ibtk_le_node_distribution returns, trailing ghost nodes included if the caller has
+ * them.  The result is byte for byte what ibtk_le_forcegen_set_* build for perm =
+ * inverse(order): the same 64-bit row offsets and the same records in the same order
+ * (springs ascending in the new k, the rank in a stable sort of the deck by perm[master];
+ * beams likewise with the roles master, next, prev within one k; target points in a
+ * stable sort by perm[node]).  A class the store does not hold becomes empty.
+ *
+ * A vertex that order does not name is absent.  A spec whose master (target point: whose
+ * vertex) is absent is dropped -- a rank holding part of the structures calls it this
+ * way; a kept spec with an absent slave, next or prev is an error.
+ *
+ * order is not trusted: an entry outside [0, num_vertex) and a Lagrangian index named
+ * twice are found by the kernel that inverts order, which range-checks every entry before
+ * it uses it as an index, and a kept spec with an absent endpoint by the key kernels;
+ * every later kernel skips what was flagged.  On any of the three the call returns
+ * IBTK_LE_ERR_ARG with a message naming the first offending entry, vertex or spec, every
+ * class of the plan is left empty and the plan invalid: ibtk_le_forcegen_compute (and the
+ * plan read-back) return IBTK_LE_ERR_ARG until a renumber or a set_* succeeds.
+ *
+ * All work is ordered on ctx's stream and the call ends with one small device-to-host
+ * read of the status record (it blocks; it is a regrid-time call, compute stays free of
+ * host synchronisation).  Its buffers are sized from the store's totals on the first
+ * call, after a wait for the stream; a later call with the same store allocates nothing.
+ * More than 2^31 - 1 entries in a class (2 per spring, 3 per beam): IBTK_LE_ERR_RANGE.
+ * compute needs U exactly when a KEPT target point has eta != 0. */
+int ibtk_le_forcegen_renumber(ibtk_le_ctx ctx, ibtk_le_forcegen fg, ibtk_le_forcespecs fs, const int* order_dev,
+                              int n_order);
+/* out[0:3] the springs, beams and target points the last renumber kept, out[3:6] those it
+ * dropped, out[6] the device bytes the plan and its renumber scratch hold, out[7] the
+ * device allocations renumber has made for this plan so far. */
+int ibtk_le_forcegen_renumber_stats(ibtk_le_forcegen fg, long long* out);
+/* The plan read back, for tests and debugging.  cls: 0 springs, 1 beams, 2 target points.
+ * *n_entries: 2 per spring, 3 per beam, 1 per target point.  plan_read copies the n_nodes
+ * + 1 row offsets and the n_entries records (rec_bytes = n_entries * the record's size,
+ * else IBTK_LE_ERR_ARG) to the host; it blocks.  Records, without padding:
+ *   springs        {int m, s; double kappa, rest;}
+ *   beams          {int m, next, prev, role; double bend, curv[ndim];}   role 0 / 1 / 2: the
+ *                  row's node is the master / next / prev
+ *   target points  {double kappa, eta, X0[ndim];} */
+int ibtk_le_forcegen_plan_size(ibtk_le_forcegen fg, int cls, long long* n_entries);
+int ibtk_le_forcegen_plan_read(ibtk_le_forcegen fg, int cls, long long* off_host, void* rec_host,
+                               long long rec_bytes);
+
 /* Position update fused with the z-slab migration classes (bench.py --move, ibamr_amd.slab.
  * migrate_device): X_new = the ibtk_le_position_update of (X_cur, U0, U1), wrapped
  * into [0, L) per dim as torch.remainder does; the markers' owners are the slabs of

@@ -12,7 +12,15 @@ Reports, on one JSON line (and into --out):
   * copy_ms: a pinned device-to-host copy of X plus a pinned host-to-device copy of F of the
     same size, the least a step pays for this stage when the forces are computed on the host.
 
+--renumber measures the regrid instead: the plan rebuilt for a new numbering of the nodes (a
+seeded random permutation), on the device (ForceGen.renumber from a DeviceForceSpecs uploaded
+once; HIP events around the call, warm-up calls, then min / median / max) and by the host
+route it replaces (ForceSpecs.arrays(perm), then ForceGen(...) through the set_* calls and
+their upload; wall clock, --host-iters times).  The two plans are compared byte for byte
+unless --no-verify.  Default --out: profiles/forcegen_renumber.json.
+
 Usage: python tools/bench_forcegen.py [--n-side N] [--iters K] [--warmup W] [--out FILE]
+       python tools/bench_forcegen.py --renumber [--n-side N] [--iters K] [--warmup W] [--host-iters H]
 """
 import argparse
 import json
@@ -52,13 +60,96 @@ def sheet(N: int, rng):
     return X, springs, beams, targets
 
 
+def renumber_bench(args):
+    import time
+
+    import torch
+
+    from ibamr_amd import build, io, le
+    from ibamr_amd.forcegen import DeviceForceSpecs, ForceGen, ForceSpecs
+
+    if not torch.cuda.is_available():
+        sys.exit("bench_forcegen: no GPU (this measurement has no CPU fallback)")
+    N, nd = args.n_side, 3
+    n = N * N
+    rng = np.random.default_rng(0)
+    _, springs, beams, targets = sheet(N, rng)
+    ns, nb, nt = springs[0].size, beams[0].size, targets[0].size
+    sp = ForceSpecs(nd, targets[3], io.SpringDeck(*springs, np.zeros(ns, dtype=np.int32), []), io.BeamDeck(*beams),
+                    io.TargetDeck(*targets[:3]))
+    perm = rng.permutation(n)            # perm[lagrangian index] = node
+    order = np.argsort(perm).astype(np.int32)  # order[node] = lagrangian index
+    ctx = le.Context(0)
+    t0 = time.perf_counter()
+    ds = DeviceForceSpecs(ctx, sp)
+    ctx.synchronize()
+    store_s = time.perf_counter() - t0
+    order_dev = torch.from_numpy(order).cuda()
+    fg = ForceGen(ctx, n, nd)
+    ms = []
+    for it in range(args.warmup + args.iters):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fg.renumber(ds, order_dev)
+        e1.record()
+        e1.synchronize()
+        if it >= args.warmup:
+            ms.append(e0.elapsed_time(e1))
+    stats = fg.renumber_stats()
+
+    host_s, host_arrays_s = [], []
+    fh = None
+    for _ in range(args.host_iters):
+        fh = None  # the earlier host plan's memory goes back first
+        t0 = time.perf_counter()
+        a = sp.arrays(perm)
+        t1 = time.perf_counter()
+        fh = ForceGen(ctx, n, nd, a["springs"], a["beams"], a["targets"])
+        ctx.synchronize()
+        t2 = time.perf_counter()
+        host_arrays_s.append(t1 - t0)
+        host_s.append(t2 - t0)
+    same = None
+    if not args.no_verify and fh is not None:
+        same = all(np.array_equal(x[0], y[0]) and np.array_equal(x[1].view(np.uint8), y[1].view(np.uint8))
+                   for x, y in ((fg.plan(c), fh.plan(c)) for c in range(3)))
+    rec = {"spring": 24, "beam": 24 + 8 * nd, "target": 16 + 8 * nd}
+    plan = 3 * 8 * (n + 1) + 2 * ns * rec["spring"] + 3 * nb * rec["beam"] + nt * rec["target"]
+    r3 = lambda v: round(v, 3)  # noqa: E731
+    res = {
+        "bench": "forcegen_renumber", "source_hash": build.source_hash(), "device": torch.cuda.get_device_name(0),
+        "n_side": N, "nodes": n, "springs": ns, "beams": nb, "targets": nt, "iters": args.iters,
+        "warmup": args.warmup, "host_iters": args.host_iters, "plan_bytes": plan,
+        "plan_bytes_per_node": round(plan / n, 1),
+        "device_rebuild_ms": {"min": r3(min(ms)), "median": r3(statistics.median(ms)), "max": r3(max(ms))},
+        "device_bytes_held": stats["bytes"], "device_allocations": stats["allocations"],
+        "spec_store_upload_s": r3(store_s),
+        "host_route_s": ({"min": r3(min(host_s)), "median": r3(statistics.median(host_s)), "max": r3(max(host_s)),
+                          "arrays_median": r3(statistics.median(host_arrays_s))} if host_s else "not measured"),
+        "plans_equal": same,
+    }
+    if host_s:
+        res["host_over_device"] = round(statistics.median(host_s) * 1e3 / statistics.median(ms), 1)
+    print(json.dumps(res))
+    out = Path(args.out or ROOT / "profiles" / "forcegen_renumber.json")
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(json.dumps(res, indent=1) + "\n")
+    if same is False:
+        sys.exit("bench_forcegen: the rebuilt plan differs from the host plan")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--n-side", type=int, default=3162)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default="")
+    ap.add_argument("--renumber", action="store_true", help="time the plan rebuild at a renumbering instead")
+    ap.add_argument("--host-iters", type=int, default=2, help="--renumber: timed runs of the host route")
+    ap.add_argument("--no-verify", action="store_true", help="--renumber: skip the byte comparison of the plans")
     args = ap.parse_args()
+    if args.renumber:
+        return renumber_bench(args)
 
     import torch
 
