@@ -138,6 +138,14 @@ _SIGS = [
     ("ibtk_le_forcegen_renumber_stats", c_int, [c_void_p, ctypes.POINTER(ctypes.c_longlong)]),
     ("ibtk_le_forcegen_plan_size", c_int, [c_void_p, c_int, ctypes.POINTER(ctypes.c_longlong)]),
     ("ibtk_le_forcegen_plan_read", c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_longlong]),
+    ("ibtk_le_rodgen_create", c_int, [c_void_p, c_int, ctypes.POINTER(c_void_p)]),
+    ("ibtk_le_rodgen_destroy", c_int, [c_void_p]),
+    ("ibtk_le_rodgen_set_rods", c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    ("ibtk_le_rodgen_compute", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int]),
+    ("ibtk_le_rodgen_plan_size", c_int, [c_void_p, ctypes.POINTER(ctypes.c_longlong)]),
+    ("ibtk_le_rodgen_plan_read", c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_longlong]),
+    ("ibtk_le_director_update", c_int,
+     [c_void_p, c_int, ctypes.c_longlong, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("ibtk_le_slab_update_partition", c_int,
      [c_void_p, c_int, ctypes.c_longlong, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
       c_int, c_void_p, c_void_p]),

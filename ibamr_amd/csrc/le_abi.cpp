@@ -3688,3 +3688,22 @@ extern "C" int ibtk_le_forcegen_plan_read(ibtk_le_forcegen fg, int cls, long lon
     HIP_TRY(hipMemcpy(rec_host, rec.p, (size_t)want, hipMemcpyDeviceToHost));
     return IBTK_LE_OK;
 }
+
+// ---------------------------------------------------------------------------
+// What the Kirchhoff rod path (le_rod.hip, le_rod.h) needs of this file: the calling
+// thread's last error and a context's device and stream.
+// ---------------------------------------------------------------------------
+namespace ibtk_le {
+int abi_fail(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    return fail(code, "%s", buf);
+}
+void abi_ctx_device_stream(ibtk_le_ctx_s* ctx, int* device, hipStream_t* stream) {
+    *device = ctx->device;
+    *stream = ctx->stream;
+}
+}  // namespace ibtk_le

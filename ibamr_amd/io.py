@@ -19,6 +19,13 @@ These formats let marker data move between this library and an IBAMR run:
   parameters.  ``ibamr_amd.forcegen.ForceSpecs`` turns them into the flat arrays
   ``IBStandardForceGen`` caches.
 
+* ``.rod`` and ``.director`` files, the decks of ``IBKirchhoffRodForceGen`` /
+  ``GeneralizedIBMethod`` (readers: ``IBStandardInitializer.cpp:1407-1700``,
+  ``:2137-2260``; samples: ``examples/IB/explicit/ex4/curve3d_64.*``).  A ``.rod`` line
+  holds an edge ``curr next`` and ten material parameters; a ``.director`` file holds
+  three lines per vertex, the triad ``D1 D2 D3``.  ``ibamr_amd.rods.RodSpecs`` turns them
+  into the arrays the rod force generator caches.
+
 * The ``LNodeIndex`` stream record (``ibtk/include/ibtk/private/LNodeIndex-inl.h:148-172``):
   three ``int`` (Lagrangian index, global PETSc index, local PETSc index), then
   the periodic offset ``int[NDIM]``, then the periodic displacement
@@ -47,6 +54,7 @@ __all__ = [
     "read_vertex", "write_vertex",
     "SpringDeck", "BeamDeck", "TargetDeck",
     "read_spring", "write_spring", "read_beam", "write_beam", "read_target", "write_target",
+    "RodDeck", "read_rod", "write_rod", "read_director", "write_director",
     "lnode_index_dtype", "lnode_index_stream_size", "pack_lnode_indices", "unpack_lnode_indices",
     "pack_ltransaction", "unpack_ltransaction",
 ]
@@ -361,6 +369,120 @@ def write_target(path: str | os.PathLike, node, kappa, eta=None) -> None:
             row += f" {float(eta[k]):.16e}"
         rows.append(row)
     _write_deck(path, rows)
+
+
+class RodDeck(NamedTuple):
+    """A ``.rod`` file in deck order, edges as written: ``curr`` is the master."""
+    curr: np.ndarray    # (n,) int32
+    next: np.ndarray    # (n,) int32
+    params: np.ndarray  # (n, 10) float64: ds a1 a2 a3 b1 b2 b3 kappa1 kappa2 tau
+
+
+ROD_PARAMS = ("ds", "a1", "a2", "a3", "b1", "b2", "b3", "kappa1", "kappa2", "tau")
+
+
+def read_rod(path: str | os.PathLike, num_vertex: int, vertex_offset: int = 0,
+             uniform_rod_properties: Optional[Sequence[float]] = None) -> RodDeck:
+    """Read a ``.rod`` file: per line ``curr next ds a1 a2 a3 b1 b2 b3 [kappa1 [kappa2 [tau]]]``.
+
+    Follows IBStandardInitializer::readRodFiles (IBStandardInitializer.cpp:1455-1688):
+    indices are checked against ``[0, num_vertex)`` before ``vertex_offset`` is added, a
+    negative ``ds``, ``a*`` or ``b*`` is an error, missing curvature fields are 0 (the
+    reference only warns when some but not all are given), ``uniform_rod_properties`` (10
+    values) replaces a line's whole property vector (:1664-1667), and the edge is kept as
+    written -- ``curr`` is the master (:1681-1684); unlike a spring's, the smaller index
+    does not become the master.
+    """
+    uni = None if uniform_rod_properties is None else np.asarray(uniform_rod_properties, dtype=np.float64)
+    if uni is not None and uni.shape != (10,):
+        raise ValueError("uniform_rod_properties must have 10 entries")
+    with _Deck(path, "rod") as deck:
+        n = deck.count()
+        curr, nxt = np.empty(n, np.int32), np.empty(n, np.int32)
+        params = np.zeros((n, 10))
+        for k in range(n):
+            tok = deck.tokens()
+            curr[k] = deck.index(tok, 0, num_vertex) + vertex_offset
+            nxt[k] = deck.index(tok, 1, num_vertex) + vertex_offset
+            for j in range(7):
+                params[k, j] = deck.value(tok, 2 + j, f"rod material constant {ROD_PARAMS[j]} is negative")
+            for j in range(7, 10):
+                try:
+                    params[k, j] = float(tok[2 + j])
+                except (IndexError, ValueError):
+                    break  # the stream extraction fails from here on: the remaining fields stay 0
+            if uni is not None:
+                params[k] = uni
+    return RodDeck(curr, nxt, params)
+
+
+def write_rod(path: str | os.PathLike, curr, next, params) -> None:
+    """Write a ``.rod`` file with all ten parameters (``%.16e``: a read gives the same
+    doubles back)."""
+    params = np.asarray(params, dtype=np.float64).reshape(-1, 10)
+    if params.shape[0] != len(curr) or len(next) != len(curr):
+        raise ValueError("curr, next and params must have one entry per rod")
+    rows = [f"{int(curr[k]):6d} {int(next[k]):6d}" + "".join(f" {float(v):.16e}" for v in params[k])
+            for k in range(len(curr))]
+    _write_deck(path, rows)
+
+
+_ROOT_EPS = float(np.sqrt(np.finfo(np.float64).eps))
+
+
+def _equal_eps(a: float, b: float) -> bool:
+    """``|a - b| <= sqrt(DBL_EPSILON) * max(|a|, |b|, 1)``: the rule implemented here for
+    SAMRAI's ``MathUtilities<double>::equalEps``, whose text is not in the reference tree
+    (parity unpinned)."""
+    return abs(a - b) <= _ROOT_EPS * max(abs(a), abs(b), 1.0)
+
+
+def read_director(path: str | os.PathLike, num_vertex: int) -> np.ndarray:
+    """Read a ``.director`` file into a ``(num_vertex, 9)`` float64 array, rows ``D1 D2 D3``.
+
+    Follows IBStandardInitializer::readDirectorFiles (IBStandardInitializer.cpp:2157-2240):
+    line 1 holds the count, which must equal ``num_vertex``; then three lines per vertex,
+    three components each.  A vector is divided by its norm (``sqrt`` of the squares summed
+    in component order) when the norm is not "equal to 1" in the sense of SAMRAI's
+    ``MathUtilities<double>::equalEps`` -- implemented here as ``|norm - 1| <=
+    sqrt(DBL_EPSILON) * max(norm, 1)``, SAMRAI's own text not being at hand (unpinned,
+    DESIGN.md section 2); a vector within that of unit length comes back bit for bit as
+    parsed.
+    """
+    with _Deck(path, "director") as deck:
+        tok = deck.tokens()
+        try:
+            n = int(tok[0])
+        except (IndexError, ValueError):
+            raise deck.invalid() from None
+        if n != num_vertex:
+            raise deck.invalid()
+        D = np.empty((n, 9), dtype=np.float64)
+        for k in range(n):
+            for r in range(3):
+                tok = deck.tokens()
+                norm2 = 0.0
+                for d in range(3):
+                    try:
+                        v = float(tok[d])
+                    except (IndexError, ValueError):
+                        raise deck.invalid() from None
+                    D[k, 3 * r + d] = v
+                    norm2 += v * v
+                norm = float(np.sqrt(norm2))
+                if not _equal_eps(norm, 1.0):
+                    D[k, 3 * r:3 * r + 3] /= norm
+    return D
+
+
+def write_director(path: str | os.PathLike, D) -> None:
+    """Write ``D`` (N, 9) as a ``.director`` file, three ``%.16e`` lines per vertex."""
+    D = np.asarray(D, dtype=np.float64)
+    if D.ndim != 2 or D.shape[1] != 9 or D.shape[0] == 0:
+        raise ValueError("D must be (N>0, 9)")
+    with open(os.fspath(path), "w") as fh:
+        fh.write(f"{D.shape[0]}\n")
+        np.savetxt(fh, D.reshape(-1, 3), fmt="%.16e", delimiter=" ")
 
 
 def _aligned(nbytes: int, align: int) -> int:

@@ -635,6 +635,81 @@ int ibtk_le_forcegen_plan_size(ibtk_le_forcegen fg, int cls, long long* n_entrie
 int ibtk_le_forcegen_plan_read(ibtk_le_forcegen fg, int cls, long long* off_host, void* rec_host,
                                long long rec_bytes);
 
+/* ---- Kirchhoff rods (IBKirchhoffRodForceGen, GeneralizedIBMethod) ---------------------
+ * The Lagrangian side of the generalized IB step, 3-D and fp64: the force F and torque N
+ * of IBKirchhoffRodForceGen::computeLagrangianForceAndTorque (IBKirchhoffRodForceGen.cpp:
+ * 326-527) from the positions X and the director triads D ([n_nodes][9], rows D1 D2 D3),
+ * and the rotation of the triads by the interpolated angular velocity
+ * (GeneralizedIBMethod::eulerStep / trapezoidalStep, GeneralizedIBMethod.cpp:326-447).
+ * W and N themselves travel through ibtk_le_interp / ibtk_le_spread as depth-3 data.
+ *
+ * Rod k (curr, next, ds a1 a2 a3 b1 b2 b3 kappa1 kappa2 tau), :401-469:
+ *   A = sum_i D_i[next] D_i[curr]^T,  D_i_half = sqrt(A) D_i[curr]  (the principal root)
+ *   dX = X[next] - X[curr]
+ *   F_half = b1 (D1_half . dX/ds) D1_half + b2 (D2_half . dX/ds) D2_half
+ *            + b3 (D3_half . dX/ds - 1) D3_half
+ *   N_half = a1 ((D2[next] - D2[curr])/ds . D3_half - kappa1) D1_half
+ *            + a2 ((D3[next] - D3[curr])/ds . D1_half - kappa2) D2_half
+ *            + a3 ((D1[next] - D1[curr])/ds . D2_half - tau) D3_half
+ *   F[curr] += F_half,  N[curr] += N_half + 0.5 dX x F_half
+ *   F[next] -= F_half,  N[next] += -N_half + 0.5 dX x F_half
+ * The reference adds all curr contributions in ascending k and then all next contributions
+ * in ascending k (two VecSetValuesBlocked(ADD_VALUES) calls per vector, :489-515).  The
+ * plan keeps that list per node -- one CSR over the nodes with 64-bit row offsets, two
+ * entries per rod, a node's curr-role entries in ascending k and then its next-role
+ * entries in ascending k, every entry the whole rod {int curr, next; double p[10];} (88
+ * bytes, no padding; the row's node is the curr end when record.curr == node) -- and one
+ * kernel, a lane per node, evaluates every rod of its row and sums in list order: no
+ * atomics, bit-stable run to run, and the two ends of a rod see the identical F_half and
+ * N_half.
+ *
+ * The principal square root is computed for a general 3x3 matrix (the triads drift; A is
+ * not assumed to be a rotation) by a Denman-Beavers iteration capped at a compile-time
+ * count; sqrt(I) is I exactly.  The reference takes Eigen's Schur-based root: the results
+ * agree to rounding, not bit for bit.  An A with an eigenvalue on the closed negative real
+ * axis (neighbouring triads half a turn apart) has no principal root and the reference's
+ * result there is unspecified: F and N of the two nodes of such a rod may be anything,
+ * NaN included; no other node is affected.
+ *
+ * set_rods takes HOST arrays of NODE indices in [0, n_nodes) and params[n][10], in the
+ * reference's order (ibamr_amd.rods.RodSpecs.arrays), validates them on the host before
+ * any device call (IBTK_LE_ERR_ARG with a message: a NULL handle, n < 0, a NULL array with
+ * n > 0, an index out of range, curr == next, a non-finite parameter; ds == 0 is accepted
+ * as the reference accepts it -- it divides by it and the result is inf or NaN), builds
+ * the plan with a stable counting sort and replaces the plan with a blocking upload (n = 0
+ * clears it).  A failed call leaves the plan as it was (the new plan goes into fresh device
+ * buffers that replace the old ones once it is uploaded).  A handle created with ctx NULL
+ * only validates: a set_rods with valid arguments and n > 0 then returns IBTK_LE_ERR_ARG
+ * ("without a context").
+ *
+ * compute: F = F + acc (accumulate_F != 0) or F = acc, likewise N, on [n_nodes][3] device
+ * arrays, ordered on the context stream: no allocation, no host synchronisation.  (The
+ * reference adds to the F the standard generator left and zeroes N first,
+ * GeneralizedIBMethod.cpp:488.)  With no rods set, F and N are left untouched when
+ * accumulating and zeroed otherwise.  F and N must not overlap each other, X or D.  ctx must
+ * be the context the handle was created with (IBTK_LE_ERR_ARG otherwise): set_rods and
+ * destroy wait for that context's stream before they release the plan's buffers. */
+typedef struct ibtk_le_rodgen_s* ibtk_le_rodgen;
+int ibtk_le_rodgen_create(ibtk_le_ctx ctx, int n_nodes, ibtk_le_rodgen* out);
+int ibtk_le_rodgen_destroy(ibtk_le_rodgen rg);
+int ibtk_le_rodgen_set_rods(ibtk_le_rodgen rg, int n, const int* curr, const int* next, const double* params);
+int ibtk_le_rodgen_compute(ibtk_le_ctx ctx, ibtk_le_rodgen rg, const double* X_dev, const double* D_dev,
+                           double* F_dev, double* N_dev, int accumulate_F, int accumulate_N);
+/* The plan read back, for tests and debugging: *n_entries = 2 per rod; plan_read copies the
+ * n_nodes + 1 row offsets and the records (rec_bytes = n_entries * 88, else
+ * IBTK_LE_ERR_ARG) to the host; it blocks. */
+int ibtk_le_rodgen_plan_size(ibtk_le_rodgen rg, long long* n_entries);
+int ibtk_le_rodgen_plan_read(ibtk_le_rodgen rg, long long* off_host, void* rec_host, long long rec_bytes);
+/* The director update over n nodes: e = W0 (IBTK_LE_EULER) or 0.5 (W0 + W1)
+ * (IBTK_LE_TRAPEZOIDAL; W1 is ignored and may be NULL otherwise), [n][3] each.  Where
+ * |e| > DBL_EPSILON the three rows of D ([n][9]) are rotated by the Rodrigues matrix of
+ * GeneralizedIBMethod.cpp:357-361 with theta = |e| dt and e /= |e|; elsewhere they are
+ * copied bit for bit.  IBTK_LE_MIDPOINT returns IBTK_LE_ERR_ARG, as the reference refuses
+ * it (:383-389).  D_new may be D_cur itself; any other overlap of D_new with D_cur, W0 or
+ * W1 is IBTK_LE_ERR_ARG.  Ordered on the context stream, no host synchronisation. */
+int ibtk_le_director_update(ibtk_le_ctx ctx, int scheme, long long n, double dt, const double* D_cur_dev,
+                            const double* W0_dev, const double* W1_dev, double* D_new_dev);
+
 /* Position update fused with the z-slab migration classes (bench.py --move, ibamr_amd.slab.
  * migrate_device): X_new = the ibtk_le_position_update of (X_cur, U0, U1), wrapped
  * into [0, L) per dim as torch.remainder does; the markers' owners are the slabs of
