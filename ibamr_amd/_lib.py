@@ -146,6 +146,9 @@ _SIGS = [
     ("ibtk_le_rodgen_plan_read", c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_longlong]),
     ("ibtk_le_director_update", c_int,
      [c_void_p, c_int, ctypes.c_longlong, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("ibtk_le_curl_side", c_int,
+     [c_void_p, ctypes.POINTER(PatchGeom), ctypes.POINTER(c_void_p), ctypes.POINTER(PatchGeom),
+      ctypes.POINTER(c_void_p), c_double, c_int, c_void_p]),
     ("ibtk_le_slab_update_partition", c_int,
      [c_void_p, c_int, ctypes.c_longlong, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
       c_int, c_void_p, c_void_p]),

@@ -15,6 +15,7 @@
 
 #include "../../include/ibtk_le.h"
 #include "le_internal.h"
+#include "le_curl.h"
 
 using namespace ibtk_le;
 
@@ -2330,6 +2331,84 @@ extern "C" int ibtk_le_phys_bdry_side(ibtk_le_ctx ctx, const ibtk_le_patch_geom*
     for (int i = 0; i < nd * 2 * nd; ++i) coef[i] = BdCoef{acoef[i], bcoef[i], gcoef[i]};
     if (set_device(ctx)) return IBTK_LE_ERR_DEVICE;
     HIP_TRY(launch_phys_bdry_side(P, phys, coef, adjoint ? 1 : 0, ctx->stream));
+    return IBTK_LE_OK;
+}
+// PatchMathOps::curl(side, side) with the scale / axpy of GeneralizedIBMethod::
+// interpolateVelocity and spreadForce (GeneralizedIBMethod.cpp:292-319, 537-577): every
+// check runs on the host before the one launch, so a refused call writes nothing.
+extern "C" int ibtk_le_curl_side(ibtk_le_ctx ctx, const ibtk_le_patch_geom* u_geom, const double* const* u_dev,
+                                 const ibtk_le_patch_geom* w_geom, double* const* w_dev, double alpha, int accumulate,
+                                 const int* periodic) {
+    if (!ctx || !u_geom || !w_geom || !u_dev || !w_dev) return fail(IBTK_LE_ERR_ARG, "curl_side: null argument");
+    if (u_geom->ndim != 3 || w_geom->ndim != 3)
+        return fail(IBTK_LE_ERR_ARG, "curl_side: ndim must be 3 (got %d and %d)", u_geom->ndim, w_geom->ndim);
+    for (int d = 0; d < 3; ++d) {
+        if (u_geom->ilower[d] != w_geom->ilower[d] || u_geom->iupper[d] != w_geom->iupper[d])
+            return fail(IBTK_LE_ERR_ARG, "curl_side: the boxes of u and w differ in dim %d", d);
+        if (!(u_geom->dx[d] == w_geom->dx[d]) && !(std::isnan(u_geom->dx[d]) && std::isnan(w_geom->dx[d])))
+            return fail(IBTK_LE_ERR_ARG, "curl_side: dx of u and w differ in dim %d", d);
+        if (!std::isfinite(u_geom->dx[d]) || u_geom->dx[d] == 0.0)
+            return fail(IBTK_LE_ERR_ARG, "curl_side: dx[%d] must be finite and non-zero", d);
+        if (u_geom->gcw[d] < 0 || w_geom->gcw[d] < 0) return fail(IBTK_LE_ERR_ARG, "curl_side: negative ghost width");
+    }
+    for (int a = 0; a < 3; ++a)
+        if (!u_dev[a] || !w_dev[a]) return fail(IBTK_LE_ERR_ARG, "curl_side: null side array %d", a);
+    for (int d = 0; d < 3; ++d)
+        if (u_geom->iupper[d] < u_geom->ilower[d]) return IBTK_LE_OK;  // an empty box: nothing to write
+    for (int d = 0; d < 3; ++d)
+        if (!(periodic && periodic[d]) && u_geom->gcw[d] < 1)
+            return fail(IBTK_LE_ERR_GHOST_WIDTH,
+                        "curl_side: insufficient ghost cells: u needs a ghost width of 1 in the non-periodic dim %d", d);
+    CurlSide P;
+    std::memset(&P, 0, sizeof(P));
+    const char* lo_b[6];
+    const char* hi_b[6];
+    for (int side = 0; side < 2; ++side) {
+        const ibtk_le_patch_geom* g = side ? w_geom : u_geom;
+        // the pitch covers the widest array (the ghosted box + 1 face) and a plane stays below 2^28 points
+        const long long m0 = (long long)g->iupper[0] - g->ilower[0] + 2 + 2LL * g->gcw[0];
+        const long long m1 = (long long)g->iupper[1] - g->ilower[1] + 2 + 2LL * g->gcw[1];
+        if (!packed(g) && (g->pitch[0] < m0 || (g->pitch[1] != 0 && g->pitch[1] < m1)))
+            return fail(IBTK_LE_ERR_ARG, "curl_side: array pitch {%d, %d} below the ghosted extent {%lld, %lld} (+1 face)",
+                        g->pitch[0], g->pitch[1], m0, m1);
+        if (8 * ((packed(g) ? m0 : g->pitch[0]) * (!packed(g) && g->pitch[1] ? g->pitch[1] : m1)) >= (1LL << 31))
+            return fail(IBTK_LE_ERR_ARG, "curl_side: an array plane exceeds 2^28 points");
+        for (int a = 0; a < 3; ++a) {
+            int64_t n[3], s1, s2, sd;
+            for (int d = 0; d < 3; ++d) n[d] = (int64_t)g->iupper[d] - g->ilower[d] + 1 + 2 * g->gcw[d] + (d == a ? 1 : 0);
+            array_strides(g, n, s1, s2, sd);
+            const double* const base = side ? w_dev[a] : u_dev[a];
+            lo_b[3 * side + a] = (const char*)base;
+            hi_b[3 * side + a] = (const char*)(base + (n[2] - 1) * s2 + (n[1] - 1) * s1 + n[0]);
+            if (side) {
+                P.w[a] = w_dev[a];
+                P.ws1[a] = s1;
+                P.ws2[a] = s2;
+            } else {
+                P.u[a] = u_dev[a];
+                P.us1[a] = s1;
+                P.us2[a] = s2;
+                for (int d = 0; d < 3; ++d) P.uhi[a][d] = g->iupper[d] + g->gcw[d] + (d == a ? 1 : 0);
+            }
+        }
+    }
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b)
+            if (lo_b[3 + a] < hi_b[b] && lo_b[b] < hi_b[3 + a])
+                return fail(IBTK_LE_ERR_ARG, "curl_side: w array %d overlaps u array %d (the curl does not run in place)",
+                            a, b);
+    for (int d = 0; d < 3; ++d) {
+        P.ilo[d] = u_geom->ilower[d];
+        P.ihi[d] = u_geom->iupper[d];
+        P.ulo[d] = u_geom->ilower[d] - u_geom->gcw[d];
+        P.wlo[d] = w_geom->ilower[d] - w_geom->gcw[d];
+        P.fac[d] = 0.125 / u_geom->dx[d];
+        P.per[d] = periodic && periodic[d] ? 1 : 0;
+    }
+    P.alpha = alpha;
+    P.accumulate = accumulate ? 1 : 0;
+    if (set_device(ctx)) return IBTK_LE_ERR_DEVICE;
+    HIP_TRY(launch_curl_side(P, ctx->stream));
     return IBTK_LE_OK;
 }
 extern "C" int ibtk_le_position_update(ibtk_le_ctx ctx, int scheme, long long n, double dt, const double* X_cur_dev,

@@ -370,6 +370,41 @@ int ibtk_le_fold_periodic_ghosts(ibtk_le_ctx ctx, const ibtk_le_patch_geom* geom
 int ibtk_le_phys_bdry_side(ibtk_le_ctx ctx, const ibtk_le_patch_geom* geom, double* const* u_dev,
                            const int* physical, const double* acoef, const double* bcoef, const double* gcoef,
                            int adjoint);
+/* The side-centred curl of a side-centred field on one 3-D patch, fp64:
+ *   w = alpha * curl u         (accumulate == 0)
+ *   w = alpha * curl u + w     (accumulate != 0)
+ * over the patch's three side boxes -- PatchMathOps::curl(side, side), the arithmetic of
+ * stoscurl3d (ibtk/src/math/fortran/curl3d.f.m4:457-559) -- the Eulerian operator on either
+ * side of the generalized IB coupling calls: GeneralizedIBMethod::interpolateVelocity forms
+ * w = 0.5 curl u before it interpolates W (GeneralizedIBMethod.cpp:292-319), spreadForce
+ * adds f += 0.5 curl n after it spreads N (:537-577).  u_dev[a] / w_dev[a]: the ghosted
+ * side array of axis a.  Each component is fac * (an eight-term sum taken left to right in
+ * the reference's operand order), fac = 0.125 / dx[d] one division, the difference of two
+ * such terms, then t = alpha * c rounded once (the reference's scale pass) and, when
+ * accumulating, w = t + w rounded once (its axpy): bit for bit the reference's values, no
+ * contraction.  Nothing outside the three side boxes of w is written (no ghost point, no
+ * row padding) and u is never written.
+ *
+ * u_geom and w_geom agree in ndim (3), ilower, iupper and dx; they may differ in gcw and
+ * pitch (packed and pitched layouts are honoured, as in the other 3-D single-patch calls).
+ *
+ * periodic: NULL or all zeros is the PLAIN ROUTINE, which is the reference's: it reads u's
+ * ghost layer as it stands and needs u_geom->gcw[d] >= 1 in every dim
+ * (IBTK_LE_ERR_GHOST_WIDTH otherwise).  NULL means "none" here -- unlike
+ * ibtk_le_fill_periodic_ghosts and ibtk_le_fill_interp, where NULL means every dim.  Where
+ * periodic[d] != 0, a read outside the cell range of dim d is taken at its periodic image
+ * by ibtk_le_fill_periodic_ghosts' rule for side data (index i reads ilower + (i - ilower)
+ * mod n, the face iupper + 1 of an array's own axis included): bit for bit
+ * ibtk_le_fill_periodic_ghosts(u) followed by the plain call, without writing u and
+ * without needing a ghost layer (or a box of 2 gcw + 1 cells) in that dim.
+ *
+ * IBTK_LE_ERR_ARG, with nothing written: ndim != 3; boxes or dx that differ; a null
+ * pointer; any w array overlapping any u array (the curl does not run in place); a
+ * non-finite or zero dx.  An empty box is IBTK_LE_OK and writes nothing.  One launch on the
+ * context stream, no host synchronisation, no allocation. */
+int ibtk_le_curl_side(ibtk_le_ctx ctx, const ibtk_le_patch_geom* u_geom, const double* const* u_dev,
+                      const ibtk_le_patch_geom* w_geom, double* const* w_dev, double alpha, int accumulate,
+                      const int* periodic);
 /* Local numbering of one patch's markers (LDataManager::computeNodeDistribution,
  * LDataManager.cpp:2839-3027, cells by IndexUtilities::getCellIndex): order_dev[i]
  * is the input index of the marker given local index i.  Markers whose cell is in
