@@ -149,6 +149,15 @@ _SIGS = [
     ("ibtk_le_curl_side", c_int,
      [c_void_p, ctypes.POINTER(PatchGeom), ctypes.POINTER(c_void_p), ctypes.POINTER(PatchGeom),
       ctypes.POINTER(c_void_p), c_double, c_int, c_void_p]),
+    ("ibtk_le_imp_interp", c_int,
+     [c_void_p, c_void_p, ctypes.POINTER(PatchGeom), ctypes.POINTER(c_void_p), c_void_p, c_void_p, c_void_p]),
+    ("ibtk_le_imp_spread", c_int,
+     [c_void_p, c_void_p, ctypes.POINTER(PatchGeom), ctypes.POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_int]),
+    ("ibtk_le_imp_deformation_update", c_int,
+     [c_void_p, c_int, c_int, ctypes.c_longlong, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("ibtk_le_imp_stress", c_int,
+     [c_void_p, c_int, ctypes.c_longlong, c_void_p, c_void_p, c_double, c_double, c_double, c_void_p, c_int,
+      c_void_p]),
     ("ibtk_le_slab_update_partition", c_int,
      [c_void_p, c_int, ctypes.c_longlong, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
       c_int, c_void_p, c_void_p]),

@@ -16,6 +16,7 @@
 #include "../../include/ibtk_le.h"
 #include "le_internal.h"
 #include "le_curl.h"
+#include "le_imp.h"
 
 using namespace ibtk_le;
 
@@ -152,6 +153,7 @@ struct ibtk_le_ctx_s {
     DevBuf sink;  // 64 doubles (Params::sink)
     DevBuf stamps;  // diagnostic phase clocks (IBTK_LE_STAMPS=1)
     DevBuf mig_cls, mig_cnt;  // ibtk_le_slab_update_partition scratch
+    DevBuf imp_skey, imp_sval, imp_start;  // ibtk_le_imp_spread: the list sorted by anchor cell, the cell offsets
     bool stamps_on = false;  // IBTK_LE_STAMPS=1, read once at ctx_create
     bool count_adds = false; // ibtk_le_ctx_count_adds: the spread sweeps count their ds_add_f64
     DevBuf adds;             // the device counters
@@ -278,7 +280,8 @@ extern "C" int ibtk_le_ctx_destroy(ibtk_le_ctx ctx) {
                        &ctx->lst2_idx, &ctx->lst2_xs, &ctx->lst2_cell, &ctx->lst_flag, &ctx->num_tab, &ctx->num_lkey,
                        &ctx->num_ckey, &ctx->ll_cnt, &ctx->ll_key, &ctx->ll_key2, &ctx->ll_id, &ctx->ll_id2,
                        &ctx->ll_src, &ctx->ll_img, &ctx->ll_off,
-                       &ctx->lvl_tab, &ctx->zero_tab, &ctx->mig_cls, &ctx->mig_cnt, &ctx->adds})
+                       &ctx->lvl_tab, &ctx->zero_tab, &ctx->mig_cls, &ctx->mig_cnt, &ctx->adds,
+                       &ctx->imp_skey, &ctx->imp_sval, &ctx->imp_start})
         b->release();
     if (ctx->ev0) hipEventDestroy(ctx->ev0);
     if (ctx->ev1) hipEventDestroy(ctx->ev1);
@@ -2409,6 +2412,184 @@ extern "C" int ibtk_le_curl_side(ibtk_le_ctx ctx, const ibtk_le_patch_geom* u_ge
     P.accumulate = accumulate ? 1 : 0;
     if (set_device(ctx)) return IBTK_LE_ERR_DEVICE;
     HIP_TRY(launch_curl_side(P, ctx->stream));
+    return IBTK_LE_OK;
+}
+// ---------------------------------------------------------------------------
+// IMPMethod: velocity gradient interp, stress spread, F update, stress (le_imp.hip).
+// Every check runs on the host before the first launch, so a refused call writes nothing.
+// ---------------------------------------------------------------------------
+static int imp_check_geom(const char* who, const ibtk_le_patch_geom* geom) {
+    if (!geom) return fail(IBTK_LE_ERR_ARG, "%s: null geometry", who);
+    if (geom->ndim != 2 && geom->ndim != 3) return fail(IBTK_LE_ERR_ARG, "%s: ndim must be 2 or 3 (got %d)", who, geom->ndim);
+    if (int rc = check_geom(geom)) return rc;
+    for (int d = 0; d < geom->ndim; ++d) {
+        if (!std::isfinite(geom->dx[d]) || !std::isfinite(geom->x_lower[d]))
+            return fail(IBTK_LE_ERR_ARG, "%s: dx and x_lower must be finite", who);
+        // LEInteractor::getMinimumGhostWidth("IB_6") = 4: IMPMethod's kernel has IB_6's stencil
+        if (geom->gcw[d] < IMP_MIN_GHOST)
+            return fail(IBTK_LE_ERR_GHOST_WIDTH, "%s: insufficient ghost cells: the IMP kernel needs %d, ghost width %d in dim %d",
+                        who, IMP_MIN_GHOST, geom->gcw[d], d);
+    }
+    return IBTK_LE_OK;
+}
+
+static int imp_check_markers(const char* who, ibtk_le_ctx ctx, ibtk_le_markers m, const ibtk_le_patch_geom* geom) {
+    if (!ctx || !m) return fail(IBTK_LE_ERR_ARG, "%s: null ctx/markers", who);
+    if (m->ctx != ctx) return fail(IBTK_LE_ERR_ARG, "%s: the markers belong to another context", who);
+    if (m->kernel != K_IB_6)
+        return fail(IBTK_LE_ERR_ARG, "%s: markers were binned for kernel %s, not IB_6", who,
+                    m->kernel >= 0 ? kNames[m->kernel] : "(none)");
+    if (m->npatch) return fail(IBTK_LE_ERR_ARG, "%s: markers were binned for a level", who);
+    if (m->n_dev) return fail(IBTK_LE_ERR_ARG, "%s: a fixed-capacity list (markers_bin_count) is not supported", who);
+    if (!same_geom(m->geom, *geom)) return fail(IBTK_LE_ERR_ARG, "%s: markers were binned for a different patch geometry", who);
+    return IBTK_LE_OK;
+}
+
+// the three side components in IMPMethod's frame (:487-496); clip 0: the ghost boxes, 1: toSideBox(patch_box, c)
+static void imp_params(ibtk_le_markers m, const ibtk_le_patch_geom* g, double* const* arrays, int clip, ImpParams& P) {
+    std::memset(&P, 0, sizeof(P));
+    const int nd = g->ndim;
+    P.ndim = nd;
+    P.n = m->n;
+    P.sorted_X = m->sorted_X.as<double>();
+    P.sorted_X_ref = m->xcur_set ? m->xcur.as<double*>() : nullptr;
+    P.sorted_s = m->sorted_s.as<int>();
+    P.K = ib6_K();
+    for (int d = 0; d < 3; ++d) {
+        P.dx[d] = d < nd ? g->dx[d] : 1.0;
+        P.xlo[d] = d < nd ? g->x_lower[d] : 0.0;
+        P.ilower[d] = d < nd ? g->ilower[d] : 0;
+    }
+    for (int c = 0; c < nd; ++c) {
+        ImpComp& C = P.comp[c];
+        C.u = arrays[c];
+        int64_t n[3] = {1, 1, 1};
+        for (int d = 0; d < nd; ++d) {
+            C.lo[d] = g->ilower[d] - g->gcw[d];
+            C.hi[d] = g->iupper[d] + g->gcw[d] + (d == c ? 1 : 0);
+            C.clo[d] = clip ? g->ilower[d] : C.lo[d];
+            C.chi[d] = clip ? g->iupper[d] + (d == c ? 1 : 0) : C.hi[d];
+            C.xlo[d] = g->x_lower[d] + (d == c ? -0.5 * g->dx[d] : 0.0);
+            n[d] = C.hi[d] - C.lo[d] + 1;
+        }
+        int64_t sd;
+        array_strides(g, n, C.s1, C.s2, sd);
+    }
+}
+
+extern "C" int ibtk_le_imp_interp(ibtk_le_ctx ctx, ibtk_le_markers m, const ibtk_le_patch_geom* geom,
+                                  const double* const* u_dev, double* U_dev, double* GradU_dev, const double* X_dev) {
+    if (int rc = imp_check_geom("imp_interp", geom)) return rc;
+    if (!u_dev) return fail(IBTK_LE_ERR_ARG, "imp_interp: null array table");
+    for (int c = 0; c < geom->ndim; ++c)
+        if (!u_dev[c]) return fail(IBTK_LE_ERR_ARG, "imp_interp: null side array %d", c);
+    if (int rc = imp_check_markers("imp_interp", ctx, m, geom)) return rc;
+    if (m->n == 0) return IBTK_LE_OK;
+    if (!U_dev || !GradU_dev || !X_dev) return fail(IBTK_LE_ERR_ARG, "imp_interp: null U, GradU or X");
+    if (set_device(ctx)) return IBTK_LE_ERR_DEVICE;
+    if (int rc = build_dedup(ctx, m)) return rc;
+    ImpParams P;
+    imp_params(m, geom, const_cast<double* const*>(u_dev), 0, P);
+    P.qdst = m->has_dups ? m->qdst.as<int>() : nullptr;
+    P.U = U_dev;
+    P.GradU = GradU_dev;
+    HIP_TRY(launch_imp_interp(P, ctx->stream));
+    return IBTK_LE_OK;
+}
+
+extern "C" int ibtk_le_imp_spread(ibtk_le_ctx ctx, ibtk_le_markers m, const ibtk_le_patch_geom* geom, double* const* f_dev,
+                                  const double* tau_dev, const double* wgt_dev, const double* X_dev, int clip) {
+    if (int rc = imp_check_geom("imp_spread", geom)) return rc;
+    if (clip != IBTK_LE_IMP_CLIP_PATCH && clip != IBTK_LE_IMP_CLIP_GHOST)
+        return fail(IBTK_LE_ERR_ARG, "imp_spread: unknown clip %d", clip);
+    if (!f_dev) return fail(IBTK_LE_ERR_ARG, "imp_spread: null array table");
+    for (int c = 0; c < geom->ndim; ++c)
+        if (!f_dev[c]) return fail(IBTK_LE_ERR_ARG, "imp_spread: null side array %d", c);
+    if (int rc = imp_check_markers("imp_spread", ctx, m, geom)) return rc;
+    if (m->n == 0) return IBTK_LE_OK;
+    if (!tau_dev || !wgt_dev || !X_dev) return fail(IBTK_LE_ERR_ARG, "imp_spread: null tau, wgt or X");
+    const int nd = geom->ndim, n = m->n;
+    ImpParams P;
+    imp_params(m, geom, f_dev, clip == IBTK_LE_IMP_CLIP_PATCH, P);
+    P.tau = tau_dev;
+    P.wgt = wgt_dev;
+    P.dV = nd == 3 ? (geom->dx[0] * geom->dx[1]) * geom->dx[2] : geom->dx[0] * geom->dx[1];
+    long long ncells = 1;
+    const int B = nd == 3 ? IMP_TILE3 : IMP_TILE2;
+    for (int d = 0; d < 3; ++d) {
+        if (d >= nd) {
+            P.alo[d] = 0;
+            P.aext[d] = 1;
+            P.nt[d] = 1;
+            continue;
+        }
+        P.alo[d] = geom->ilower[d] - geom->gcw[d] - (IMP_REACH + 1);
+        P.aext[d] = (geom->iupper[d] + geom->gcw[d] + 1 + (IMP_REACH + 1)) - P.alo[d] + 1;
+        ncells *= P.aext[d];
+        // tiles from each component's clip lower corner; the widest clip box has one face more
+        const int ext = P.comp[d].chi[d] - P.comp[d].clo[d] + 1;
+        P.nt[d] = (ext + B - 1) / B;
+    }
+    if (ncells + 1 >= (1LL << 31)) return fail(IBTK_LE_ERR_RANGE, "imp_spread: patch too large for 31-bit anchor cells");
+    P.ncells = (int)ncells;
+    if (set_device(ctx)) return IBTK_LE_ERR_DEVICE;
+    int rc;
+    if ((rc = ctx->keys_in.ensure(sizeof(unsigned) * (size_t)n))) return rc;
+    if ((rc = ctx->vals_in.ensure(sizeof(int) * (size_t)n))) return rc;
+    if ((rc = ctx->imp_skey.ensure(sizeof(unsigned) * (size_t)n))) return rc;
+    if ((rc = ctx->imp_sval.ensure(sizeof(int) * (size_t)n))) return rc;
+    if ((rc = ctx->imp_start.ensure(sizeof(int) * ((size_t)ncells + 1)))) return rc;
+    P.keys = ctx->keys_in.as<unsigned>();
+    P.vals = ctx->vals_in.as<int>();
+    P.svals = ctx->imp_sval.as<int>();
+    P.start = ctx->imp_start.as<int>();
+    const hipStream_t s = ctx->stream;
+    HIP_TRY(launch_imp_keys(P, s));
+    int end_bit = 1;
+    while ((1ULL << end_bit) <= (unsigned long long)ncells) ++end_bit;
+    size_t tb = 0;
+    HIP_TRY(launch_sort(nullptr, tb, P.keys, ctx->imp_skey.as<unsigned>(), P.vals, ctx->imp_sval.as<int>(), n, end_bit, s));
+    if ((rc = ctx->temp.ensure(tb))) return rc;
+    tb = ctx->temp.cap;
+    HIP_TRY(launch_sort(ctx->temp.p, tb, P.keys, ctx->imp_skey.as<unsigned>(), P.vals, ctx->imp_sval.as<int>(), n, end_bit, s));
+    HIP_TRY(launch_key_offsets(ctx->imp_skey.as<unsigned>(), n, 1u, P.ncells, ctx->imp_start.as<int>(), s));
+    HIP_TRY(launch_imp_spread(P, s));
+    return IBTK_LE_OK;
+}
+
+extern "C" int ibtk_le_imp_deformation_update(ibtk_le_ctx ctx, int ndim, int scheme, long long n, double dt,
+                                              const double* F_cur_dev, const double* G0_dev, const double* G1_dev,
+                                              double* F_new_dev, double* F_half_dev) {
+    if (ndim != 2 && ndim != 3) return fail(IBTK_LE_ERR_ARG, "imp_deformation_update: ndim must be 2 or 3 (got %d)", ndim);
+    if (scheme < IBTK_LE_EULER || scheme > IBTK_LE_TRAPEZOIDAL)
+        return fail(IBTK_LE_ERR_ARG, "imp_deformation_update: unknown update scheme %d", scheme);
+    if (n < 0) return fail(IBTK_LE_ERR_ARG, "imp_deformation_update: negative length");
+    if (scheme == IBTK_LE_TRAPEZOIDAL && n > 0 && !G1_dev)
+        return fail(IBTK_LE_ERR_ARG, "imp_deformation_update: TRAPEZOIDAL needs G1 (Grad U at the new time)");
+    if (scheme != IBTK_LE_EULER && F_half_dev)
+        return fail(IBTK_LE_ERR_ARG, "imp_deformation_update: only EULER produces F_half");
+    if (n > 0 && (!F_cur_dev || !G0_dev || !F_new_dev)) return fail(IBTK_LE_ERR_ARG, "imp_deformation_update: null array");
+    if (!ctx) return fail(IBTK_LE_ERR_ARG, "imp_deformation_update: null context");
+    if (n == 0) return IBTK_LE_OK;
+    if (set_device(ctx)) return IBTK_LE_ERR_DEVICE;
+    // F_new = inv(I - dt/2 Gb)(I + dt/2 Ga) F: Ga = Gb = G0, but TRAPEZOIDAL's Gb = G1 (:587, :643, :703)
+    const double* const Gb = scheme == IBTK_LE_TRAPEZOIDAL ? G1_dev : G0_dev;
+    HIP_TRY(launch_imp_update(ndim, n, dt, F_cur_dev, G0_dev, Gb, F_new_dev, F_half_dev, ctx->stream));
+    return IBTK_LE_OK;
+}
+
+extern "C" int ibtk_le_imp_stress(ibtk_le_ctx ctx, int ndim, long long n, const double* F_dev, double* tau_dev, double c1,
+                                  double p0, double beta, const double* table_dev, int nsub, const int* subdomain_dev) {
+    if (ndim != 2 && ndim != 3) return fail(IBTK_LE_ERR_ARG, "imp_stress: ndim must be 2 or 3 (got %d)", ndim);
+    if (n < 0) return fail(IBTK_LE_ERR_ARG, "imp_stress: negative length");
+    if ((table_dev != nullptr) != (subdomain_dev != nullptr))
+        return fail(IBTK_LE_ERR_ARG, "imp_stress: a parameter table and a subdomain array go together");
+    if (table_dev && nsub < 1) return fail(IBTK_LE_ERR_ARG, "imp_stress: the parameter table needs nsub >= 1 rows");
+    if (n > 0 && (!F_dev || !tau_dev)) return fail(IBTK_LE_ERR_ARG, "imp_stress: null array");
+    if (!ctx) return fail(IBTK_LE_ERR_ARG, "imp_stress: null context");
+    if (n == 0) return IBTK_LE_OK;
+    if (set_device(ctx)) return IBTK_LE_ERR_DEVICE;
+    HIP_TRY(launch_imp_stress(ndim, n, F_dev, tau_dev, c1, p0, beta, table_dev, nsub, subdomain_dev, ctx->stream));
     return IBTK_LE_OK;
 }
 extern "C" int ibtk_le_position_update(ibtk_le_ctx ctx, int scheme, long long n, double dt, const double* X_cur_dev,

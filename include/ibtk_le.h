@@ -745,6 +745,69 @@ int ibtk_le_rodgen_plan_read(ibtk_le_rodgen rg, long long* off_host, void* rec_h
 int ibtk_le_director_update(ibtk_le_ctx ctx, int scheme, long long n, double dt, const double* D_cur_dev,
                             const double* W0_dev, const double* W1_dev, double* D_new_dev);
 
+/* ---- IMPMethod: the immersed material point method ------------------------------------
+ * The four device stages of src/IB/IMPMethod.cpp for one patch of side-centred data, 2-D and
+ * 3-D.  IMPMethod carries its own IB_6 kernel with its derivative (:119-171): the same NINT
+ * anchor and six points as "IB_6", but the powers of r are running products (r3 = r r2, ...)
+ * where the Fortran kernels use binary powering, so its weights are not ibtk_le_interp's to
+ * the last bit.  The component frame is the reference's: x_lower[d] - 0.5 dx[d] and iupper[d]
+ * + 1 for d == component.
+ *
+ * m: markers binned with kernel IB_6 on `geom` (ibtk_le_markers_bin; list entries, indices,
+ * Xshift and duplicates as in ibtk_le_interp), not a level and not a fixed-capacity list.
+ * geom->gcw[d] >= 4 in every dim (IBTK_LE_ERR_GHOST_WIDTH otherwise).  Positions are the
+ * binned ones, X(s) + Xshift(l).  DEVIATION: the reference evaluates its kernel at X(s) and
+ * ignores the periodic offset of an image node; with Xshift = 0 the two agree.
+ *
+ * ibtk_le_imp_interp (IMPMethod::interpolateVelocity :460-536): U_dev[s][NDIM] and
+ * GradU_dev[s][NDIM * i + j] = d u_i / d x_j, from the stencil box clipped to the
+ * component's ghost box, summed with dimension 0 fastest, w = (phi0 phi1) phi2,
+ * U(c) += u w, dw_k = ((a_0) a_1) a_2 with a_d = dphi[d] / dx[d] for d == k and phi[d]
+ * otherwise, Grad_U(c, k) -= u dw_k: bit for bit the reference's values.  Rows the list does
+ * not name are not written; of duplicate entries the last one writes.  One launch (the first
+ * interp after a binning with an index list also builds the duplicate table, which
+ * synchronises, as ibtk_le_interp does).
+ *
+ * ibtk_le_imp_spread (::spreadForce :848-921): f(i_s) += (sum_k tau(c,k) dw_k) wgt / dV_c,
+ * dV_c = (dx0 dx1) dx2, tau_dev[s][NDIM * c + k], wgt_dev[s].  clip = IBTK_LE_IMP_CLIP_PATCH
+ * is the reference: the stencil is cut to toSideBox(patch_box, c), periodic images arrive
+ * as list entries (ibtk_le_periodic_index_list); IBTK_LE_IMP_CLIP_GHOST cuts to the arrays'
+ * ghost boxes, for a caller who then folds (ibtk_le_fold_periodic_ghosts) or applies
+ * ibtk_le_phys_bdry_side(adjoint).  Nothing outside the clip boxes is written.  No atomics:
+ * every point sums its contributions itself, in a fixed order (by anchor cell, list order
+ * within a cell), so the result is bit-identical from run to run; it differs from the
+ * reference's by that order and by f (wgt / dV) for (f wgt) / dV.  Four launches and a device
+ * sort on the context stream, no host synchronisation.
+ *
+ * ibtk_le_imp_deformation_update (eulerStep, midpointStep, trapezoidalStep :547-716), rows
+ * of NDIM^2 doubles: F_new = inv(I - dt/2 Gb)(I + dt/2 G0) F_cur with Gb = G0 (EULER: Grad U
+ * at the current time; MIDPOINT: at the half time) or G1 (TRAPEZOIDAL: G0 current, G1 new;
+ * G1 NULL is IBTK_LE_ERR_ARG).  EULER also writes F_half (dt/4 for dt/2) unless F_half_dev
+ * is NULL; with another scheme a non-NULL F_half_dev is IBTK_LE_ERR_ARG.  tensor_inverse is
+ * the cofactor form of ibtk/libmesh_utilities.h:310-339, in 2-D its 2x2 branch with
+ * F(2,2) = 1.  F_new may be F_cur.
+ *
+ * ibtk_le_imp_stress: tau = PP FF^T (IMPMethod::computeLagrangianForce :756-764) with the
+ * law of examples/IMP/explicit/ex0/main.cpp:68-89, PP = 2 c1 FF, - 2 p0 FF^-T when p0 != 0,
+ * + beta log(det(FF^T FF)) FF^-T when beta != 0.  table_dev NULL: the scalars c1, p0, beta;
+ * else point i takes row subdomain_dev[i] (int32) of table_dev[nsub][3] = {c1, p0, beta}
+ * and the scalars are ignored (a row outside [0, nsub) gives that point a NaN stress).  The
+ * reference's registered PK1 function is a host pointer; here tau is a device array, so a
+ * caller may fill it by other means.
+ *
+ * The update and the stress validate before they need the context, so a NULL ctx with valid
+ * arguments returns IBTK_LE_ERR_ARG ("null context"). */
+enum { IBTK_LE_IMP_CLIP_PATCH = 0, IBTK_LE_IMP_CLIP_GHOST = 1 };
+int ibtk_le_imp_interp(ibtk_le_ctx ctx, ibtk_le_markers m, const ibtk_le_patch_geom* geom, const double* const* u_dev,
+                       double* U_dev, double* GradU_dev, const double* X_dev);
+int ibtk_le_imp_spread(ibtk_le_ctx ctx, ibtk_le_markers m, const ibtk_le_patch_geom* geom, double* const* f_dev,
+                       const double* tau_dev, const double* wgt_dev, const double* X_dev, int clip);
+int ibtk_le_imp_deformation_update(ibtk_le_ctx ctx, int ndim, int scheme, long long n, double dt,
+                                   const double* F_cur_dev, const double* G0_dev, const double* G1_dev,
+                                   double* F_new_dev, double* F_half_dev);
+int ibtk_le_imp_stress(ibtk_le_ctx ctx, int ndim, long long n, const double* F_dev, double* tau_dev, double c1, double p0,
+                       double beta, const double* table_dev, int nsub, const int* subdomain_dev);
+
 /* Position update fused with the z-slab migration classes (bench.py --move, ibamr_amd.slab.
  * migrate_device): X_new = the ibtk_le_position_update of (X_cur, U0, U1), wrapped
  * into [0, L) per dim as torch.remainder does; the markers' owners are the slabs of
