@@ -158,6 +158,15 @@ _SIGS = [
     ("ibtk_le_imp_stress", c_int,
      [c_void_p, c_int, ctypes.c_longlong, c_void_p, c_void_p, c_double, c_double, c_double, c_void_p, c_int,
       c_void_p]),
+    ("ibtk_le_sources_create", c_int,
+     [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, ctypes.POINTER(c_void_p)]),
+    ("ibtk_le_sources_destroy", c_int, [c_void_p]),
+    ("ibtk_le_source_locations", c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("ibtk_le_source_spread", c_int, [c_void_p, c_void_p, ctypes.POINTER(PatchGeom), c_void_p, c_void_p, c_void_p]),
+    ("ibtk_le_source_normalize", c_int,
+     [c_void_p, c_void_p, ctypes.POINTER(PatchGeom), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    ("ibtk_le_source_pressure", c_int,
+     [c_void_p, c_void_p, ctypes.POINTER(PatchGeom), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("ibtk_le_slab_update_partition", c_int,
      [c_void_p, c_int, ctypes.c_longlong, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
       c_int, c_void_p, c_void_p]),

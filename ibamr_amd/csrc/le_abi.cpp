@@ -313,7 +313,8 @@ extern "C" int ibtk_le_ctx_synchronize(ibtk_le_ctx ctx) {
         return fail(IBTK_LE_ERR_INVARIANT,
                     "device invariant failed (flag %d): a stencil left its staged region (1) or its bin bounds (2), "
                     "an interior list entry is not in the level's binned lists (4), a fixed-capacity "
-                    "migration overflowed (8), or the spread's candidate stream reached 2^31 entries (16)",
+                    "migration overflowed (8), the spread's candidate stream reached 2^31 entries (16), or the spread "
+                    "fluid sources do not integrate to their strengths (32)",
                     flag);
     }
     return IBTK_LE_OK;
@@ -3950,8 +3951,9 @@ extern "C" int ibtk_le_forcegen_plan_read(ibtk_le_forcegen fg, int cls, long lon
 }
 
 // ---------------------------------------------------------------------------
-// What the Kirchhoff rod path (le_rod.hip, le_rod.h) needs of this file: the calling
-// thread's last error and a context's device and stream.
+// What the Kirchhoff rod path (le_rod.hip, le_rod.h) and the source path (le_source.hip,
+// le_source.h) need of this file: the calling thread's last error, a context's device and
+// stream, and its device flag word.
 // ---------------------------------------------------------------------------
 namespace ibtk_le {
 int abi_fail(int code, const char* fmt, ...) {
@@ -3966,4 +3968,5 @@ void abi_ctx_device_stream(ibtk_le_ctx_s* ctx, int* device, hipStream_t* stream)
     *device = ctx->device;
     *stream = ctx->stream;
 }
+int* abi_ctx_flags(ibtk_le_ctx_s* ctx) { return ctx->err.as<int>(); }
 }  // namespace ibtk_le

@@ -26,6 +26,11 @@ These formats let marker data move between this library and an IBAMR run:
   three lines per vertex, the triad ``D1 D2 D3``.  ``ibamr_amd.rods.RodSpecs`` turns them
   into the arrays the rod force generator caches.
 
+* ``.source`` files, the deck of internal fluid sources and sinks (reader:
+  ``IBStandardInitializer.cpp:2495-2691``): the sources' names and radii, then the
+  vertices on each source's perimeter.  ``ibamr_amd.sources.SourceSpecs`` turns them into
+  the arrays the source plan takes.
+
 * The ``LNodeIndex`` stream record (``ibtk/include/ibtk/private/LNodeIndex-inl.h:148-172``):
   three ``int`` (Lagrangian index, global PETSc index, local PETSc index), then
   the periodic offset ``int[NDIM]``, then the periodic displacement
@@ -55,6 +60,7 @@ __all__ = [
     "SpringDeck", "BeamDeck", "TargetDeck",
     "read_spring", "write_spring", "read_beam", "write_beam", "read_target", "write_target",
     "RodDeck", "read_rod", "write_rod", "read_director", "write_director",
+    "SourceDeck", "read_source", "write_source",
     "lnode_index_dtype", "lnode_index_stream_size", "pack_lnode_indices", "unpack_lnode_indices",
     "pack_ltransaction", "unpack_ltransaction",
 ]
@@ -425,6 +431,82 @@ def write_rod(path: str | os.PathLike, curr, next, params) -> None:
     rows = [f"{int(curr[k]):6d} {int(next[k]):6d}" + "".join(f" {float(v):.16e}" for v in params[k])
             for k in range(len(curr))]
     _write_deck(path, rows)
+
+
+class SourceDeck(NamedTuple):
+    """A ``.source`` file: the sources, and the vertices that carry one."""
+    names: List[str]     # per source
+    radii: np.ndarray    # (num_source,) float64, each > 0
+    node: np.ndarray     # (n,) int32 vertices in ascending order, each once
+    source: np.ndarray   # (n,) int32 the source each carries
+
+
+def read_source(path: str | os.PathLike, num_vertex: int, vertex_offset: int = 0, source_offset: int = 0) -> SourceDeck:
+    """Read a ``.source`` file: the number of sources, that many name lines, that many radii,
+    the number of source points, then one ``vertex source`` pair per line.
+
+    Follows IBStandardInitializer::readSourceFiles (IBStandardInitializer.cpp:2495-2691): a
+    name is its line with the comment cut and the white space trimmed, a radius is ``> 0``,
+    a vertex is checked against ``[0, num_vertex)`` and a source index against
+    ``[0, num_source)`` before ``vertex_offset`` / ``source_offset`` (the sources of the files
+    read before, :2668-2673) are added.  ``d_source_idx[ln][j][n]`` is a map: a vertex listed
+    twice keeps its last source, and the deck comes back in ascending vertex order.
+    """
+    with _Deck(path, "source") as deck:
+        num_source = deck.count()
+        names = []
+        for _ in range(num_source):
+            deck.line += 1
+            line = deck.fh.readline()
+            if not line:
+                raise ValueError(f"Premature end to input file encountered before line {deck.line} of file {deck.name}")
+            names.append(_discard_comments(line).strip(" \t\n"))
+        radii = np.empty(num_source)
+        for m in range(num_source):
+            tok = deck.tokens()
+            try:
+                radii[m] = float(tok[0])
+            except (IndexError, ValueError):
+                raise deck.invalid() from None
+            if not radii[m] > 0.0:
+                raise deck.invalid("source radius is not positive")
+        num_pts = deck.count()
+        idx = {}
+        for _ in range(num_pts):
+            tok = deck.tokens()
+            n = deck.index(tok, 0, num_vertex)
+            try:
+                s = int(tok[1])
+            except (IndexError, ValueError):
+                raise deck.invalid() from None
+            if s < 0 or s >= num_source:
+                raise deck.invalid(f"meter index {s} is out of range")
+            idx[n] = s
+    node = np.array(sorted(idx), dtype=np.int32)
+    source = np.array([idx[n] for n in node.tolist()], dtype=np.int32)
+    return SourceDeck(names, radii, node + np.int32(vertex_offset), source + np.int32(source_offset))
+
+
+def write_source(path: str | os.PathLike, names: Sequence[str], radii, node, source) -> None:
+    """Write a ``.source`` file (``%.16e`` radii: a read gives the same doubles back).  A
+    name may not hold a comment character or a line break, and is written trimmed."""
+    radii = np.asarray(radii, dtype=np.float64).reshape(-1)
+    if len(names) != radii.size or radii.size == 0:
+        raise ValueError("one name and one radius per source, at least one source")
+    if len(node) != len(source) or len(node) == 0:
+        raise ValueError("node and source must have one entry per source point, at least one")
+    for name in names:
+        if any(c in name for c in _COMMENT_CHARS + "\n\r"):
+            raise ValueError(f"source name {name!r} holds a comment character or a line break")
+    with open(os.fspath(path), "w") as fh:
+        fh.write(f"{radii.size}\n")
+        for name in names:
+            fh.write(name.strip(" \t") + "\n")
+        for r in radii:
+            fh.write(f"{float(r):.16e}\n")
+        fh.write(f"{len(node)}\n")
+        for n, s in zip(node, source):
+            fh.write(f"{int(n):6d} {int(s):6d}\n")
 
 
 _ROOT_EPS = float(np.sqrt(np.finfo(np.float64).eps))

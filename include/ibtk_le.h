@@ -135,7 +135,9 @@ int ibtk_le_ctx_set_plane_window(ibtk_le_ctx ctx, int mode, int zlo, int zhi);
  * stencil left its staged region / bin bounds, 4 an interior list entry missing from a
  * level's binned lists, 8 a fixed-capacity migration overflowed, 16 a 3-D spread's
  * candidate stream reached 2^31 entries (it holds up to 4 sorted positions a marker,
- * 16 bytes of device memory a marker, kept with the binning). */
+ * 16 bytes of device memory a marker, kept with the binning), 32 the spread fluid sources
+ * do not integrate to their strengths, or the boundary offset does not cancel them
+ * (ibtk_le_source_normalize). */
 int ibtk_le_ctx_synchronize(ibtk_le_ctx ctx);
 
 /* ---- marker binning (device LIndexSetData / LDataManager re-binning) --------------
@@ -807,6 +809,81 @@ int ibtk_le_imp_deformation_update(ibtk_le_ctx ctx, int ndim, int scheme, long l
                                    double* F_new_dev, double* F_half_dev);
 int ibtk_le_imp_stress(ibtk_le_ctx ctx, int ndim, long long n, const double* F_dev, double* tau_dev, double c1, double p0,
                        double beta, const double* table_dev, int nsub, const int* subdomain_dev);
+
+/* ---- Fluid sources and sinks ---------------------------------------------------------------
+ * IBMethod::spreadFluidSource (src/IB/IBMethod.cpp:789-943) and ::interpolatePressure
+ * (:945-1069) with IBStandardSourceGen::getSourceLocations behind them
+ * (src/IB/IBStandardSourceGen.cpp:195-250), for one patch of cell-centred data of depth 1 laid
+ * out by geom (ghosts; pitch in 3-D), 2-D and 3-D.  These loops are not LEInteractor calls:
+ * the kernel function is cos_kernel(x, r) = 0.5 (1 + cos(pi x / r)) / r for |x| <= r, else 0
+ * (:124-134), per source n and dimension d with (:832-845)
+ *   R = max(floor(r_src[n] / dx[d] + 0.5), 2),  r = R dx[d],
+ *   centre cell by IndexUtilities::getCellIndex of X_src[n] in the patch frame,
+ *   half width int(r / dx[d]) + 1 (R for some spacings, R + 1 for others),
+ * and the stencil box cut to the patch box, never to the ghost box (:848).  A weight is
+ * w_d = cos_kernel(X_center - X_src[n][d], r), X_center = x_lower[d] + dx[d] (double(i -
+ * ilower[d]) + 0.5) (:854-855).  Each w_d is evaluated once per (source, dimension, cell
+ * index) into a table of the plan's workspace; the spread and the pressure interpolation read
+ * the same tables, so they are adjoint to rounding.  The tables hold R <= 16: a larger R
+ * returns IBTK_LE_ERR_ARG before anything is written (checked on the host from r_src and
+ * geom->dx).
+ *
+ * ibtk_le_sources_create takes HOST arrays: the radii r_src[n_src] (finite, > 0) and n_pts
+ * pairs (node[k], source[k]) -- node k, a local index in [0, n_nodes), carries source
+ * source[k] in [0, n_src), the IBSourceSpec of the reference's LNode; a node named twice is an
+ * error -- groups the nodes by source, each group in ascending local index, uploads the plan
+ * (blocking) and allocates every workspace the device calls use.  The device calls below
+ * run on the context stream, never synchronise with the host and allocate nothing.  ctx must
+ * be the plan's context.  destroy waits for that stream.
+ *
+ * ibtk_le_source_locations (getSourceLocations :213-230): X_src_dev[NDIM k + d] = sum_i
+ * X_dev[NDIM node_i + d] / double(count_k) over the nodes of source k in ascending local
+ * index, from 0, every quotient rounded before it is added, one lane per (k, d): bit for bit
+ * the reference's value on one rank.  A source without nodes gets 0.
+ *
+ * ibtk_le_source_spread (:828-859): q(i) += Q_src[n] wgt over the clipped box, wgt = (w0 w1)
+ * w2 (w0 w1 in 2-D); a cell reached by several sources adds them in ascending n.  A cell is
+ * owned by the lowest-numbered source whose clipped box holds it; the owner's lane adds every
+ * covering contribution in that order and stores once.  No atomics; bit-stable from run to
+ * run; nothing outside the union of the clipped boxes is written.  Two launches.
+ *
+ * ibtk_le_source_normalize (:863-941), totals_dev = {q_total, Q_sum, q_norm, integral_after}:
+ * q_total = sum q dV over the patch box, dV = (dx0 dx1) dx2, by a fixed-order two-stage
+ * reduction; Q_sum = sum_n Q_src[n] serially.  When |q_total - Q_sum| > 1e-12 and |q_total -
+ * Q_sum| / max(max_n |Q_src[n]|, 1) > 1e-12 (:877) the call does not abort as the reference
+ * does: it latches device flag 32, which ibtk_le_ctx_synchronize reports as
+ * IBTK_LE_ERR_INVARIANT.  With normalize != 0 (dom_lo / dom_hi, HOST, the domain box):
+ * q_norm = -q_total / vol, vol = double(cells of domain \ interior) dx0 dx1 dx2, interior
+ * the domain box shrunk by one cell in every dimension but the last; each such cell in the
+ * patch box gets += q_norm; integral_after is the integral again, and |integral_after| >
+ * 1e-10 max(1, max |q|) (:934) latches the same flag.  With normalize == 0, q is only read,
+ * q_norm = 0 and integral_after = q_total.  Two launches, or four.
+ *
+ * ibtk_le_source_pressure (:1005-1063): P_src_dev[n] = sum p(i) wgt - p_norm over the same
+ * clipped box, wgt = ((w0 dx0) (w1 dx1)) (w2 dx2), one workgroup per source, every lane a
+ * fixed share of the cells, then a fixed tree.  p_norm (:960-1003) = (sum p dV over the cells
+ * of domain \ interior in the patch box) / (their number times dV) -- the reference adds dV
+ * cell by cell, which differs in the last bits --; dom_lo and dom_hi both NULL: p_norm = 0.
+ *
+ * IBTK_LE_ERR_ARG before any device call: a null context, plan, geometry or array; ndim not 2
+ * or 3; a geometry whose ndim is not the plan's; a dx that is not finite and positive;
+ * exactly one of dom_lo / dom_hi, or an empty domain box; a node or source index out of
+ * range.  n_src == 0 and an empty patch box are IBTK_LE_OK and write nothing.  One patch: the
+ * reference's sums of X_src and P_src over ranks and patches, periodic images of a source
+ * (it has none: a stencil ends at the patch box) and source strategies other than the
+ * standard one are not here. */
+typedef struct ibtk_le_sources_s* ibtk_le_sources;
+int ibtk_le_sources_create(ibtk_le_ctx ctx, int ndim, int n_nodes, int n_src, const double* r_src, int n_pts,
+                           const int* node, const int* source, ibtk_le_sources* out);
+int ibtk_le_sources_destroy(ibtk_le_sources s);
+int ibtk_le_source_locations(ibtk_le_ctx ctx, ibtk_le_sources s, const double* X_dev, double* X_src_dev);
+int ibtk_le_source_spread(ibtk_le_ctx ctx, ibtk_le_sources s, const ibtk_le_patch_geom* geom, double* q_dev,
+                          const double* X_src_dev, const double* Q_src_dev);
+int ibtk_le_source_normalize(ibtk_le_ctx ctx, ibtk_le_sources s, const ibtk_le_patch_geom* geom, double* q_dev,
+                             const int* dom_lo, const int* dom_hi, const double* Q_src_dev, int normalize,
+                             double* totals_dev);
+int ibtk_le_source_pressure(ibtk_le_ctx ctx, ibtk_le_sources s, const ibtk_le_patch_geom* geom, const double* p_dev,
+                            const double* X_src_dev, double* P_src_dev, const int* dom_lo, const int* dom_hi);
 
 /* Position update fused with the z-slab migration classes (bench.py --move, ibamr_amd.slab.
  * migrate_device): X_new = the ibtk_le_position_update of (X_cur, U0, U1), wrapped
