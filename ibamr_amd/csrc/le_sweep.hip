@@ -225,74 +225,103 @@ __device__ __forceinline__ double* rebin_other(double* const* xcur, double* xa, 
 // re-binning's epoch: a split candidate stream (k_cand_write SHZ) must then be rebuilt even
 // if nothing moved.  Block 0 also clears the words past the last (mbits / wcnt[nw]) and the
 // long-list queue (nbig) the later kernels count on.
+// A workgroup takes RK_ROWS rows of BLOCK consecutive sorted entries, thread t the entries
+// e0 + r BLOCK + t: a wave's row is 64 consecutive entries from a multiple of 64 (the words
+// e / 32 and e / 32 + 1).  The loads are a dependent chain -- sorted_l, then X through the
+// list, beside it the old key -- so every row's load of a stage is issued before the first
+// value of that stage is used: RK_ROWS gathers in flight per lane, not one.  Rows past n
+// load entry n - 1 again (nothing is read past n) and store nothing.  sorted_l, the old keys
+// and the stored positions pass through once (non-temporal); the lines of X are used again,
+// by the entries of the next key plane.
+constexpr int RK_ROWS = 4;  // (2: 3 % slower; 8: 48 KB of LDS a workgroup, 28 % slower -- DESIGN.md 7.10)
+typedef double rk_d2 __attribute__((ext_vector_type(2)));
 template <int K>
 __global__ __launch_bounds__(BLOCK) void k_rekey(Params p, int n, const unsigned* kold, const int* sl,
                                                  double* const* xcur, double* xa, double* xb, unsigned* mbits,
                                                  int* wcnt, int* cin, int* cout, unsigned* zbits, int* zst, int epoch,
                                                  int nw, int* nbig) {
-    __shared__ double sx[3 * BLOCK];
-    const int e0 = blockIdx.x * BLOCK;
-    const int e = e0 + threadIdx.x;
+    __shared__ double sx[3 * BLOCK * RK_ROWS];
+    const long e0 = (long)blockIdx.x * (RK_ROWS * BLOCK);
     if (blockIdx.x == 0 && threadIdx.x == 0) {  // (a wave ending at word nw writes it 0 as well)
         mbits[nw] = 0u;
         wcnt[nw] = 0;
         *nbig = 0;
     }
-    bool mv = false;
-    int zp = 0;
-    // the last parities of the wave's two words and their state, loaded ahead of the
-    // gather (their latency hidden behind it, not added before the block's barrier)
-    unsigned zo0 = 0, zo1 = 0;
+    const bool lead = (threadIdx.x & 63) == 0;
+    bool in[RK_ROWS];
+    int ec[RK_ROWS], l[RK_ROWS], s[RK_ROWS];
+#pragma unroll
+    for (int r = 0; r < RK_ROWS; ++r) {
+        const long e = e0 + r * BLOCK + threadIdx.x;
+        in[r] = e < n;
+        ec[r] = (int)(in[r] ? e : n - 1);
+        l[r] = __builtin_nontemporal_load(sl + ec[r]);
+    }
+    // the last parities of each wave row's two words and their state, loaded ahead of the
+    // gather (their latency hidden behind it)
+    unsigned zo0[RK_ROWS], zo1[RK_ROWS];
     int zv = 0;
-    if (zbits && (threadIdx.x & 63) == 0 && e < n) {
-        zo0 = zbits[e >> 5];
-        zo1 = zbits[(e >> 5) + 1];
+    if (zbits && lead) {
+#pragma unroll
+        for (int r = 0; r < RK_ROWS; ++r) {
+            zo0[r] = zbits[ec[r] >> 5];
+            zo1[r] = zbits[(ec[r] >> 5) + 1];
+        }
         zv = zst[0];
     }
-    if (e < n) {
-        const int l = sl[e];
-        const int s = p.indices ? p.indices[l] : l;
-        const D3 x = ld3(p.X + (int64_t)3 * s);  // as k_gather_col (a fixed-capacity list's rows all exist)
+#pragma unroll
+    for (int r = 0; r < RK_ROWS; ++r) s[r] = p.indices ? p.indices[l[r]] : l[r];
+    D3 x[RK_ROWS], xs[RK_ROWS];
+    unsigned ko[RK_ROWS];
+#pragma unroll
+    for (int r = 0; r < RK_ROWS; ++r) {
+        x[r] = ld3(p.X + (int64_t)3 * s[r]);  // as k_gather_col (a fixed-capacity list's rows all exist)
+        if (p.Xshift) xs[r] = ld3(p.Xshift + (int64_t)3 * l[r]);
+    }
+#pragma unroll
+    for (int r = 0; r < RK_ROWS; ++r) ko[r] = __builtin_nontemporal_load(kold + ec[r]);
+    double* const outb = rebin_other(xcur, xa, xb);
+#pragma unroll
+    for (int r = 0; r < RK_ROWS; ++r) {
         double Xs[3];
 #pragma unroll
-        for (int d = 0; d < 3; ++d) Xs[d] = p.Xshift ? x.v[d] + p.Xshift[(int64_t)3 * l + d] : x.v[d];  // (no + 0.0: X bit for bit)
-        const unsigned k = entry_key<K>(p, l, Xs, zbits ? &zp : nullptr);
-        const unsigned ko = kold[e];
-        mv = k != ko;
+        for (int d = 0; d < 3; ++d) Xs[d] = p.Xshift ? x[r].v[d] + xs[r].v[d] : x[r].v[d];  // (no + 0.0: X bit for bit)
+        int zp = 0;  // (only the closed-form kernels are given zbits: launch_rekey_t)
+        const unsigned k = entry_key<K>(p, l[r], Xs, KT<K>::FAM == 0 ? &zp : nullptr);
+        const bool mv = in[r] && k != ko[r];
         if (mv) {
             atomicAdd(cin + k, 1);
-            atomicAdd(cout + ko, 1);
+            atomicAdd(cout + ko[r], 1);
+        }
+        const unsigned long long bal = __ballot(mv);
+        const int w = ec[r] >> 5;  // words e/32, e/32 + 1 (the second may be the zero sentinel)
+        if (lead && in[r]) {
+            mbits[w] = (unsigned)bal;
+            mbits[w + 1] = (unsigned)(bal >> 32);
+            wcnt[w] = __popc((unsigned)bal);
+            wcnt[w + 1] = __popc((unsigned)(bal >> 32));
+        }
+        if (zbits) {
+            const unsigned long long zb = __ballot(in[r] && zp != 0);
+            if (lead && in[r]) {
+                const bool same = zv != 0 && zo0[r] == (unsigned)zb && zo1[r] == (unsigned)(zb >> 32);
+                zbits[w] = (unsigned)zb;
+                zbits[w + 1] = (unsigned)(zb >> 32);
+                if (!same) zst[1] = epoch;
+            }
         }
 #pragma unroll
-        for (int d = 0; d < 3; ++d) sx[3 * threadIdx.x + d] = Xs[d];
-    }
-    const unsigned long long bal = __ballot(mv);
-    if ((threadIdx.x & 63) == 0 && e < n) {  // words e/32, e/32 + 1 (the second may be the zero sentinel)
-        const int w = e >> 5;
-        mbits[w] = (unsigned)bal;
-        mbits[w + 1] = (unsigned)(bal >> 32);
-        wcnt[w] = __popc((unsigned)bal);
-        wcnt[w + 1] = __popc((unsigned)(bal >> 32));
-    }
-    if (zbits) {
-        const unsigned long long zb = __ballot(zp != 0);
-        if ((threadIdx.x & 63) == 0 && e < n) {
-            const int w = e >> 5;
-            const bool same = zv != 0 && zo0 == (unsigned)zb && zo1 == (unsigned)(zb >> 32);
-            zbits[w] = (unsigned)zb;
-            zbits[w + 1] = (unsigned)(zb >> 32);
-            if (!same) zst[1] = epoch;
-        }
+        for (int d = 0; d < 3; ++d) sx[3 * (r * BLOCK + threadIdx.x) + d] = Xs[d];
     }
     __syncthreads();
-    const int cnt = 3 * min(BLOCK, n - e0);
-    double* out = rebin_other(xcur, xa, xb) + (int64_t)3 * e0;
+    const int cnt = 3 * (int)min((long)(RK_ROWS * BLOCK), n - e0);
+    double* out = outb + 3 * e0;
     for (int i = threadIdx.x; 2 * i < cnt; i += BLOCK) {
         if (2 * i + 1 < cnt) {
-            double2 v;
+            rk_d2 v;
             v.x = sx[2 * i];
             v.y = sx[2 * i + 1];
-            *reinterpret_cast<double2*>(out + 2 * i) = v;
+            __builtin_nontemporal_store(v, reinterpret_cast<rk_d2*>(out + 2 * i));
         } else {
             out[2 * i] = sx[2 * i];
         }
@@ -2789,7 +2818,8 @@ hipError_t launch_bin_col(int kernel, const Params& p, int n, unsigned* keys, in
 template <int K>
 hipError_t launch_rekey_t(const Params& p, const RebinBufs& r, hipStream_t s) {
     if (r.n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_rekey<K>, dim3((r.n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, p, r.n, r.kold, r.lsorted,
+    const long per = RK_ROWS * BLOCK;  // entries a workgroup
+    hipLaunchKernelGGL(k_rekey<K>, dim3((unsigned)((r.n + per - 1) / per)), dim3(BLOCK), 0, s, p, r.n, r.kold, r.lsorted,
                        r.xcur, r.xa, r.xb, r.mbits, r.wcnt, r.cin, r.cout, KT<K>::FAM == 0 ? r.zbits : nullptr,
                        r.zst, r.epoch, r.nw, r.nbig);
     return hipGetLastError();
