@@ -6,15 +6,24 @@
  * device implementation in ibamr_amd/csrc/le_bdry.hip.  The product library
  * never links, calls or falls back to it.
  *
- * PARITY STATUS: "parity unpinned" against the reference binary, for the same
- * reason as le_oracle.c: the reference routines are m4 sources
- * (ibtk/src/boundary/physical_boundary/fortran/cartphysbdryop{2,3}d.f.m4) that
- * need the absent m4 processor and SAMRAI's unvendored array-dimension macros,
- * and the reference ships no tests or recorded outputs for them.  The
- * restatement is pinned by identities instead (tests/test_oracle_bdry.py):
- * the adjoint routine is the transpose of the forward one wherever the Fortran
- * makes it so (Robin faces, extrapolated edges and corners), the forward fill
- * reproduces linear data along every extrapolation, and hand-worked values.
+ * PARITY STATUS: the arithmetic is pinned to the reference's own compiled
+ * Fortran.  oracle/build_ref.py expands
+ * ibtk/src/boundary/physical_boundary/fortran/cartphysbdryop{2,3}d.f.m4 (three
+ * m4 features: define, one include, and SAMRAI's CELL{2,3}d / SIDE{2,3}d{0,1,2}
+ * array bounds with a scalar ghost width) and compiles them with flang into
+ * oracle/_ref/libbdref_{O0,O2}.so; oracle/ref.py drives their routines box by
+ * box, and tests/test_bdry_ref_pin.py holds this file to both libraries bit for
+ * bit, fill and adjoint, 2-D and 3-D, over tests/bdry_cases.py (every face
+ * pattern, patches narrower than their ghost width, g = 16, b on either side
+ * of and at the 1e-12 Dirichlet threshold, NaN ghosts).  Not pinned, restated
+ * from the C++ text here and, apart from it, in oracle/ref.py: which boundary
+ * boxes a patch has and in which order they are visited, and the coefficient
+ * arrays, one constant per (component, face) where the reference takes any
+ * RobinBcCoefStrategy.  Beside the pin the restatement is held by identities
+ * (tests/test_oracle_bdry.py): the adjoint routine is the transpose of the
+ * forward one wherever the Fortran makes it so (Robin faces, extrapolated
+ * edges and corners), the forward fill reproduces linear data along every
+ * extrapolation, and hand-worked values.
  *
  * What is restated:
  *   CartSideRobinPhysBdryOp::setPhysicalBoundaryConditions

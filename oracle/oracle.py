@@ -10,7 +10,10 @@ Parity status: **pinned** to the reference's own Fortran, compiled by
 1e-13 / 1e-12 (the order of its integer powers is the compiler's).  Kept apart:
 ``DISCONTINUOUS_LINEAR`` 3-D spread (the reference reads an unset ``ic_center``) and
 ``PIECEWISE_CONSTANT`` markers outside the ghost box (the reference has no check; here
-they are skipped).  BSPLINE_4, USER_DEFINED, the C++ wrappers and the force generator
+they are skipped).  The arithmetic of the physical-boundary operators
+(``le_bdry_oracle.c``) is pinned the same way, bitwise at ``-O0`` and ``-O2``, to
+``oracle/_ref/libbdref_*`` (``tests/test_bdry_ref_pin.py``); which boundary boxes a patch
+has is restated.  BSPLINE_4, USER_DEFINED, the C++ wrappers and the force generator
 stay unpinned: they need SAMRAI.  See DESIGN.md §Oracle.
 The arithmetic lives in ``le_oracle.c`` (a restatement of
 ``ibtk/src/lagrangian/fortran/lagrangian_interaction{2,3}d.f.m4``); this module
@@ -559,13 +562,17 @@ def side_ghost_shape(box_lo, box_hi, gcw, axis):
     return ghost_shape(lo, hi, [gcw] * len(box_lo))[1:]
 
 
-def phys_bdry_side(box_lo, box_hi, gcw, dx, u_axes, phys, acoef, bcoef, gcoef, adjoint):
+def phys_bdry_side(box_lo, box_hi, gcw, dx, u_axes, phys, acoef, bcoef, gcoef, adjoint, backend=None):
     """CartSideRobinPhysBdryOp on one patch of side data (in place).
 
     adjoint=False: setPhysicalBoundaryConditions (CartSideRobinPhysBdryOp.cpp:358-422);
     adjoint=True: accumulateFromPhysicalBoundaryData (:429-493).  phys[2d+upper]
     flags a physical face; acoef/bcoef/gcoef have shape (ndim, 2 ndim):
-    [component axis, face location]."""
+    [component axis, face location].  backend: None for le_bdry_oracle.c, or a function
+    of the same arguments, e.g. ``oracle.ref.phys_bdry_side`` (the compiled reference
+    Fortran)."""
+    if backend is not None:
+        return backend(box_lo, box_hi, gcw, dx, u_axes, phys, acoef, bcoef, gcoef, adjoint)
     ndim = len(box_lo)
     us = []
     for a in range(ndim):

@@ -3,8 +3,11 @@
 oracle/le_bdry_oracle.c restates CartSideRobinPhysBdryOp's forward ghost fill
 (setPhysicalBoundaryConditions, CartSideRobinPhysBdryOp.cpp:358-422) and its
 adjoint fold (accumulateFromPhysicalBoundaryData, :429-493) with the arithmetic
-of cartphysbdryop{2,3}d.f.m4.  The Fortran cannot be built here and the
-reference holds no fixtures for it, so the restatement is pinned by:
+of cartphysbdryop{2,3}d.f.m4.  Its arithmetic is pinned bit for bit to the
+compiled Fortran by tests/test_bdry_ref_pin.py, where the reference tree and flang
+were at hand at build time.  The tests here need neither: the reference holds no
+fixtures for these routines, and the walk over the boundary boxes is restated from
+the C++ on both sides of that pin, so the restatement is also held by:
 
 * transposition: with homogeneous Robin data (b != 0, g = 0) the adjoint is the
   exact transpose of the fill, <f, L u> = <L^T f, u> over the interior, for every
