@@ -167,6 +167,14 @@ _SIGS = [
      [c_void_p, c_void_p, ctypes.POINTER(PatchGeom), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     ("ibtk_le_source_pressure", c_int,
      [c_void_p, c_void_p, ctypes.POINTER(PatchGeom), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("ibtk_le_meters_create", c_int,
+     [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(c_void_p)]),
+    ("ibtk_le_meters_destroy", c_int, [c_void_p]),
+    ("ibtk_le_meters_update", c_int,
+     [c_void_p, c_void_p, ctypes.POINTER(PatchGeom), c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p]),
+    ("ibtk_le_meters_read", c_int,
+     [c_void_p, c_void_p, ctypes.POINTER(PatchGeom), ctypes.POINTER(c_void_p), c_void_p, c_void_p, c_void_p]),
+    ("ibtk_le_meters_workspace", c_int, [c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong]),
     ("ibtk_le_slab_update_partition", c_int,
      [c_void_p, c_int, ctypes.c_longlong, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
       c_int, c_void_p, c_void_p]),

@@ -313,8 +313,9 @@ extern "C" int ibtk_le_ctx_synchronize(ibtk_le_ctx ctx) {
         return fail(IBTK_LE_ERR_INVARIANT,
                     "device invariant failed (flag %d): a stencil left its staged region (1) or its bin bounds (2), "
                     "an interior list entry is not in the level's binned lists (4), a fixed-capacity "
-                    "migration overflowed (8), the spread's candidate stream reached 2^31 entries (16), or the spread "
-                    "fluid sources do not integrate to their strengths (32)",
+                    "migration overflowed (8), the spread's candidate stream reached 2^31 entries (16), the spread "
+                    "fluid sources do not integrate to their strengths (32), or a flow meter's web is wider than "
+                    "max_web_nodes (64)",
                     flag);
     }
     return IBTK_LE_OK;

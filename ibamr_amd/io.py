@@ -31,6 +31,11 @@ These formats let marker data move between this library and an IBAMR run:
   vertices on each source's perimeter.  ``ibamr_amd.sources.SourceSpecs`` turns them into
   the arrays the source plan takes.
 
+* ``.inst`` files, the deck of flow meters and pressure gauges (reader:
+  ``IBStandardInitializer.cpp:2257-2493``): the instruments' names, then the vertices on each
+  meter's perimeter with their position on it.  ``ibamr_amd.instruments.MeterSpecs`` turns them
+  into the arrays the meter plan takes.
+
 * The ``LNodeIndex`` stream record (``ibtk/include/ibtk/private/LNodeIndex-inl.h:148-172``):
   three ``int`` (Lagrangian index, global PETSc index, local PETSc index), then
   the periodic offset ``int[NDIM]``, then the periodic displacement
@@ -61,6 +66,7 @@ __all__ = [
     "read_spring", "write_spring", "read_beam", "write_beam", "read_target", "write_target",
     "RodDeck", "read_rod", "write_rod", "read_director", "write_director",
     "SourceDeck", "read_source", "write_source",
+    "InstDeck", "read_inst", "write_inst",
     "lnode_index_dtype", "lnode_index_stream_size", "pack_lnode_indices", "unpack_lnode_indices",
     "pack_ltransaction", "unpack_ltransaction",
 ]
@@ -507,6 +513,94 @@ def write_source(path: str | os.PathLike, names: Sequence[str], radii, node, sou
         fh.write(f"{len(node)}\n")
         for n, s in zip(node, source):
             fh.write(f"{int(n):6d} {int(s):6d}\n")
+
+
+class InstDeck(NamedTuple):
+    """An ``.inst`` file: the instruments, and the vertices on their perimeters."""
+    names: List[str]        # per instrument
+    node: np.ndarray        # (n,) int32 vertices in ascending order, each once
+    meter: np.ndarray       # (n,) int32 the meter each lies on
+    meter_node: np.ndarray  # (n,) int32 its index on that meter's perimeter
+
+
+def read_inst(path: str | os.PathLike, num_vertex: int, vertex_offset: int = 0, instrument_offset: int = 0) -> InstDeck:
+    """Read an ``.inst`` file: the number of instruments, that many name lines, the number of
+    instrumented points, then one ``vertex meter node`` triple per line.
+
+    Follows IBStandardInitializer::readInstrumentationFiles (IBStandardInitializer.cpp:
+    2257-2493): a name is its line with the comment cut and the white space trimmed; a vertex is
+    checked against ``[0, num_vertex)``, a meter index against ``[0, num_inst)`` and a node
+    index against ``>= 0``, in that order on each line; then every meter index and every node
+    index ``0..max`` of every meter must have been met, and the meters met must be ``num_inst``
+    (:2438-2474).  ``vertex_offset`` and ``instrument_offset`` (the instruments of the files
+    read before, :2434, :2477) are added after the checks.  ``d_instrument_idx[ln][j][n]`` is a
+    map: a vertex listed twice keeps its last entry (the entries it lost still count as met, as
+    in the reference), and the deck comes back in ascending vertex order.
+    """
+    with _Deck(path, "instrumentation") as deck:
+        num_inst = deck.count()
+        names = []
+        for _ in range(num_inst):
+            deck.line += 1
+            line = deck.fh.readline()
+            if not line:
+                raise ValueError(f"Premature end to input file encountered before line {deck.line} of file {deck.name}")
+            names.append(_discard_comments(line).strip(" \t\n"))
+        num_pts = deck.count()
+        idx = {}
+        met: List[List[bool]] = []  # encountered_instrument_idx / encountered_node_idx
+        for _ in range(num_pts):
+            tok = deck.tokens()
+            n = deck.index(tok, 0, num_vertex)
+            try:
+                m = int(tok[1])
+            except (IndexError, ValueError):
+                raise deck.invalid() from None
+            if m < 0 or m >= num_inst:
+                raise deck.invalid(f"meter index {m} is out of range")
+            while len(met) <= m:
+                met.append([])
+            try:
+                k = int(tok[2])
+            except (IndexError, ValueError):
+                raise deck.invalid() from None
+            if k < 0:
+                raise deck.invalid("meter node index is negative")
+            met[m] += [False] * (k + 1 - len(met[m]))
+            met[m][k] = True
+            idx[n] = (m, k)
+        for m, nodes in enumerate(met):
+            if not nodes:
+                raise ValueError(f"Instrument index {m} not found in input file {deck.name}")
+            for k, seen in enumerate(nodes):
+                if not seen:
+                    raise ValueError(f"Node index {k} associated with meter index {m} not found in input file {deck.name}")
+        if len(met) != num_inst:
+            raise ValueError(f"Not all anticipated instrument indices were found in input file {deck.name}  Expected to find "
+                             f"{num_inst} distinct meter indices in input file")
+    node = np.array(sorted(idx), dtype=np.int32)
+    meter = np.array([idx[n][0] for n in node.tolist()], dtype=np.int32)
+    meter_node = np.array([idx[n][1] for n in node.tolist()], dtype=np.int32)
+    return InstDeck(names, node + np.int32(vertex_offset), meter + np.int32(instrument_offset), meter_node)
+
+
+def write_inst(path: str | os.PathLike, names: Sequence[str], node, meter, meter_node) -> None:
+    """Write an ``.inst`` file.  A name may not hold a comment character or a line break, and
+    is written trimmed."""
+    if len(names) == 0:
+        raise ValueError("at least one instrument")
+    if not (len(node) == len(meter) == len(meter_node)) or len(node) == 0:
+        raise ValueError("node, meter and meter_node must have one entry per instrumented point, at least one")
+    for name in names:
+        if any(c in name for c in _COMMENT_CHARS + "\n\r"):
+            raise ValueError(f"instrument name {name!r} holds a comment character or a line break")
+    with open(os.fspath(path), "w") as fh:
+        fh.write(f"{len(names)}\n")
+        for name in names:
+            fh.write(name.strip(" \t") + "\n")
+        fh.write(f"{len(node)}\n")
+        for n, m, k in zip(node, meter, meter_node):
+            fh.write(f"{int(n):6d} {int(m):6d} {int(k):6d}\n")
 
 
 _ROOT_EPS = float(np.sqrt(np.finfo(np.float64).eps))

@@ -137,7 +137,8 @@ int ibtk_le_ctx_set_plane_window(ibtk_le_ctx ctx, int mode, int zlo, int zhi);
  * candidate stream reached 2^31 entries (it holds up to 4 sorted positions a marker,
  * 16 bytes of device memory a marker, kept with the binning), 32 the spread fluid sources
  * do not integrate to their strengths, or the boundary offset does not cancel them
- * (ibtk_le_source_normalize). */
+ * (ibtk_le_source_normalize), flag 64 a flow meter's web is wider than the plan's max_web_nodes
+ * (ibtk_le_meters_update). */
 int ibtk_le_ctx_synchronize(ibtk_le_ctx ctx);
 
 /* ---- marker binning (device LIndexSetData / LDataManager re-binning) --------------
@@ -884,6 +885,95 @@ int ibtk_le_source_normalize(ibtk_le_ctx ctx, ibtk_le_sources s, const ibtk_le_p
                              double* totals_dev);
 int ibtk_le_source_pressure(ibtk_le_ctx ctx, ibtk_le_sources s, const ibtk_le_patch_geom* geom, const double* p_dev,
                             const double* X_src_dev, double* P_src_dev, const int* dom_lo, const int* dom_hi);
+
+/* ---- Flow meters and pressure gauges ---------------------------------------------------------
+ * IBInstrumentPanel (src/IB/IBInstrumentPanel.cpp) for one 3-D patch of side-centred u and
+ * cell-centred p of depth 1 laid out by geom (ghosts; pitch), on one rank:
+ * initializeHierarchyDependentData (:698-923) with init_meter_elements (:133-194), and
+ * readInstrumentData (:925-1182) with linear_interp (:315-501) and compute_flow_correction
+ * (:199-234).  A 2-D geometry returns IBTK_LE_ERR_ARG: the reference aborts there (:121-127).
+ * The arithmetic is + - * /, sqrt, ceil and floor, written operation for operation with the
+ * associations of the reference's Eigen 3.2.1 expressions (a fixed-size reduction is unrolled
+ * as halves, Eigen/src/Core/Redux.h:77-106: a.dot(b) = a0 b0 + (a1 b1 + a2 b2), norm = sqrt(x^2
+ * + (y^2 + z^2)); v / s divides, v /= s multiplies by 1 / s), so every output is the reference's one-rank value bit for bit (a NaN is a
+ * NaN: its sign and payload are the processor's).
+ *
+ * ibtk_le_meters_create takes HOST arrays: n_pts triples (node[k], meter[k], meter_node[k]) --
+ * local node node[k] in [0, n_nodes) is perimeter node meter_node[k] of meter meter[k] in [0,
+ * n_meters), the IBInstrumentationSpec of the reference's LNode.  P_l = 1 + the largest node
+ * index of meter l (:589-625).  IBTK_LE_ERR_ARG: an index out of range, a local node named
+ * twice, a (meter, node index) pair named twice or missing, max_web_nodes odd or < 2.
+ * max_web_nodes is the capacity of a web in the radial direction: its size follows the
+ * device-resident X, so the host cannot size it; the workspace holds sum_l P_l max_web_nodes
+ * web patches, and P_l max_web_nodes <= 4096 for every meter (IBTK_LE_ERR_ARG beyond: a
+ * meter's sort keys fill 32 KiB of LDS).  create uploads the plan (blocking) and allocates every
+ * workspace; update and read are one launch each on the context stream, never synchronise
+ * with the host and allocate nothing.  ctx must be the plan's context.  destroy waits for that
+ * stream.  n_meters == 0 is IBTK_LE_OK and every later call writes nothing; so is an empty box.
+ *
+ * ibtk_le_meters_update, for one level that is one patch: X_perimeter[l][n] = X_dev[3 node];
+ * X_centroid[l] the serial sum over n from 0, each component then multiplied by 1.0 /
+ * double(P_l) (:784-792: Eigen's v /= s multiplies by Scalar(1) / s, SelfCwiseBinaryOp.h:181-193); r_max[l] = max_n norm(X_perimeter - X_centroid) (:795-803); nw_l = 2
+ * int(ceil(r_max / h_finest)) (:828); the web centroids X_web[l][m][n] and area vectors
+ * dA_web[l][m][n], m < P_l, n < nw_l (:133-194).  Each web patch and each meter centroid gets
+ * its cell by IndexUtilities::getCellIndex in the domain frame (dom_lo, dom_hi, dom_xlo,
+ * dom_xup: HOST, 3 each) with geom->dx (:881-882, :903-904), and is counted iff that cell lies
+ * in the patch box (:889, :911); nothing periodic is applied and an uncounted web patch is
+ * dropped silently, as in the reference.  nw_l > max_web_nodes (or an r_max / h_finest no int
+ * holds) latches device flag 64, which ibtk_le_ctx_synchronize reports as
+ * IBTK_LE_ERR_INVARIANT: that meter's values are NaN until an update fits it, the other meters
+ * are unaffected.  r_max == 0 gives nw = 0: flow 0 - correction, mean pressure 0 / 0, point
+ * pressure as usual.
+ *
+ * ibtk_le_meters_read: values_dev[3 l + {0, 1, 2}] = {flow, mean pressure, point pressure} of
+ * meter l from u_dev[3] (side, the arrays of the three axes), p_dev (cell) and the marker
+ * velocities U_dev[3 node + d], with the box of the last update.  For a counted web patch in
+ * cell i, X_cell[d] = x_lower[d] + dx[d] (double(i_d - ilower[d]) + 0.5) (:990-996); the side
+ * rule (:434-501) shifts 0..1 along the axis and -1..0 or 0..1 across it by X[d] < X_cell[d],
+ * X_side carries the -0.5 dx offset on the axis, and the lower side of cell i + shift is read;
+ * the cell rule is :315-369; in both wgt = (w0 w1) w2, w_d = (X[d] < Xc[d] ? X[d] - (Xc[d] -
+ * dx[d]) : (Xc[d] + dx[d]) - X[d]) / dx[d], i2 outermost and i0 innermost, U += v wgt from 0.
+ * Per meter flow += U . dA, mean += P norm(dA), A += norm(dA), mean /= A (:1073); the point
+ * pressure is the cell rule at the centroid if the centroid is counted, else 0 (:1056); the
+ * correction (:199-234, :1142-1156) is subtracted from the flow.  The three sums are serial
+ * from +0.0 in the reference's order: the cells of the patch box with x fastest and, within
+ * a cell, the meter's web patches with m ascending, then n.  No floating-point atomics; the
+ * same bits from run to run.  u_dev == NULL skips the flow sum (flow = 0 - correction), p_dev
+ * == NULL both pressures (NaN and 0).  The rules read one ghost layer: a ghost width < 1 in
+ * any dimension is IBTK_LE_ERR_GHOST_WIDTH.  A box other than the last update's, or a read
+ * before any update, is IBTK_LE_ERR_ARG.
+ *
+ * ibtk_le_meters_workspace copies one array of the plan's workspace into dst_dev (device,
+ * `count` elements, which must be the array's size) on the context stream.  With L meters, S
+ * = sum P_l perimeter nodes and W = S max_web_nodes: X_CENTROID 3 L doubles; NUM_WEB_NODES L
+ * ints (-1: not representable); X_WEB, DA_WEB 3 W doubles and CELL 3 W ints, COUNTED W ints
+ * -- meter l's patches start at patch max_web_nodes (P_0 + ... + P_{l-1}), patch (m, n) the
+ * (m nw_l + n)-th of them; a meter that latched flag 64 keeps what it held --; CENTROID_CELL
+ * 4 L ints (the cell, then counted); X_PERIMETER 3 S doubles.
+ *
+ * Not here: more than one level or patch ("the finest level that contains the point" and the
+ * sums over ranks), z-slabs, a cell-centred u, the Silo plot output, restart, and
+ * d_total_flow_volume (one multiply-add for the caller). */
+typedef struct ibtk_le_meters_s* ibtk_le_meters;
+enum {
+    IBTK_LE_METERS_X_CENTROID = 0,
+    IBTK_LE_METERS_NUM_WEB_NODES = 1,
+    IBTK_LE_METERS_X_WEB = 2,
+    IBTK_LE_METERS_DA_WEB = 3,
+    IBTK_LE_METERS_CELL = 4,
+    IBTK_LE_METERS_COUNTED = 5,
+    IBTK_LE_METERS_CENTROID_CELL = 6,
+    IBTK_LE_METERS_X_PERIMETER = 7
+};
+int ibtk_le_meters_create(ibtk_le_ctx ctx, int n_nodes, int n_meters, int n_pts, const int* node, const int* meter,
+                          const int* meter_node, int max_web_nodes, ibtk_le_meters* out);
+int ibtk_le_meters_destroy(ibtk_le_meters mt);
+int ibtk_le_meters_update(ibtk_le_ctx ctx, ibtk_le_meters mt, const ibtk_le_patch_geom* geom, const int* dom_lo,
+                          const int* dom_hi, const double* dom_xlo, const double* dom_xup, double h_finest,
+                          const double* X_dev);
+int ibtk_le_meters_read(ibtk_le_ctx ctx, ibtk_le_meters mt, const ibtk_le_patch_geom* geom, const double* const* u_dev,
+                        const double* p_dev, const double* U_dev, double* values_dev);
+int ibtk_le_meters_workspace(ibtk_le_ctx ctx, ibtk_le_meters mt, int which, void* dst_dev, long long count);
 
 /* Position update fused with the z-slab migration classes (bench.py --move, ibamr_amd.slab.
  * migrate_device): X_new = the ibtk_le_position_update of (X_cur, U0, U1), wrapped
