@@ -138,6 +138,18 @@ _SIGS = [
     ("ibtk_le_forcegen_renumber_stats", c_int, [c_void_p, ctypes.POINTER(ctypes.c_longlong)]),
     ("ibtk_le_forcegen_plan_size", c_int, [c_void_p, c_int, ctypes.POINTER(ctypes.c_longlong)]),
     ("ibtk_le_forcegen_plan_read", c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_longlong]),
+    ("ibtk_le_forcejac_create", c_int, [c_void_p, c_void_p, ctypes.POINTER(c_void_p)]),
+    ("ibtk_le_forcejac_destroy", c_int, [c_void_p]),
+    ("ibtk_le_forcejac_rebuild", c_int, [c_void_p, c_void_p]),
+    ("ibtk_le_forcejac_assemble", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_double, ctypes.c_double]),
+    ("ibtk_le_forcejac_apply", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    ("ibtk_le_forcejac_pattern", c_int, [c_void_p, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(c_void_p),
+                                         ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p)]),
+    ("ibtk_le_forcejac_read", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong]),
+    ("ibtk_le_forcejac_stats", c_int, [c_void_p, ctypes.POINTER(ctypes.c_longlong)]),
+    ("ibtk_le_forcegen_linearized", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_double,
+                                            ctypes.c_double, c_void_p, c_int]),
+    ("ibtk_le_forcegen_jacobian_nnz", c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     ("ibtk_le_rodgen_create", c_int, [c_void_p, c_int, ctypes.POINTER(c_void_p)]),
     ("ibtk_le_rodgen_destroy", c_int, [c_void_p]),
     ("ibtk_le_rodgen_set_rods", c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),

@@ -3386,6 +3386,7 @@ struct ibtk_le_forcegen_s {
     long long ns = 0, nb = 0, nt = 0;  // springs, beams, target points in the plan
     bool need_U = false;               // some target point has eta != 0
     bool valid = true;                 // false after a failed renumber, until a renumber or a set_* succeeds
+    long long gen = 0;                 // the plan's generation: bumped by whatever replaces a class of it (ibtk_le_forcejac)
     // ibtk_le_forcegen_renumber: the inverse numbering, two key / value buffers for the
     // sorts, the specs' deck indices in the new order, rocPRIM's scratch, the status record
     DevBuf rn_perm, rn_k0, rn_k1, rn_v0, rn_v1, rn_dv, rn_temp, rn_st;
@@ -3518,6 +3519,7 @@ extern "C" int ibtk_le_forcegen_set_springs(ibtk_le_forcegen fg, int n, const in
                         k, fcn_idx[k]);
     }
     fg->ns = 0;
+    ++fg->gen;
     if (n == 0) return fg_valid(fg);
     std::vector<int> cnt(fg->n, 0);
     for (int k = 0; k < n; ++k) {
@@ -3550,6 +3552,7 @@ extern "C" int ibtk_le_forcegen_set_beams(ibtk_le_forcegen fg, int n, const int*
         if (mastr[k] == prev[k]) return fail(IBTK_LE_ERR_ARG, "beam %d: master and prev are both node %d", k, mastr[k]);
     }
     fg->nb = 0;
+    ++fg->gen;
     if (n == 0) return fg_valid(fg);
     const int rc = fg->ndim == 2 ? fg_set_beams<2>(fg, n, mastr, next, prev, bend, curv)
                                  : fg_set_beams<3>(fg, n, mastr, next, prev, bend, curv);
@@ -3567,6 +3570,7 @@ extern "C" int ibtk_le_forcegen_set_targets(ibtk_le_forcegen fg, int n, const in
         if (int rc = fg_node(fg, "target point", "its", k, node[k])) return rc;
     fg->nt = 0;
     fg->need_U = false;
+    ++fg->gen;
     if (n == 0) return fg_valid(fg);
     const int rc = fg->ndim == 2 ? fg_set_targets<2>(fg, n, node, kappa, eta, X0)
                                  : fg_set_targets<3>(fg, n, node, kappa, eta, X0);
@@ -3871,6 +3875,7 @@ extern "C" int ibtk_le_forcegen_renumber(ibtk_le_ctx ctx, ibtk_le_forcegen fg, i
                     2LL * fs->ns, 3LL * fs->nb);
     const long long total[3] = {fs->ns, fs->nb, fs->nt};
     // from here on the old plan is gone, whatever happens
+    ++fg->gen;
     fg->ns = fg->nb = fg->nt = 0;
     fg->need_U = false;
     for (int c = 0; c < 3; ++c) {
@@ -3948,6 +3953,296 @@ extern "C" int ibtk_le_forcegen_plan_read(ibtk_le_forcegen fg, int cls, long lon
     HIP_TRY(hipStreamSynchronize(fg->ctx->stream));
     HIP_TRY(hipMemcpy(off_host, off.p, sizeof(long long) * ((size_t)fg->n + 1), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(rec_host, rec.p, (size_t)want, hipMemcpyDeviceToHost));
+    return IBTK_LE_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The force Jacobian (ibtk_le_forcejac; the kernels are le_force_jac.hip's): a block-CSR
+// pattern built on the device from a force generator's current plan, its values, the
+// product with a vector; beside it the linearized force and the preallocation counts
+// straight from the plan.
+// ---------------------------------------------------------------------------
+struct ibtk_le_forcejac_s {
+    ibtk_le_ctx ctx = nullptr;
+    ibtk_le_forcegen fg = nullptr;
+    long long gen = -1;     // fg->gen the pattern was built from; -1: no pattern
+    long long nnzb = 0;     // blocks
+    long long ncand = 0;    // candidates: n + 2 springs + 9 beams
+    bool assembled = false;
+    DevBuf rowptr, col, val;
+    DevBuf brow, bstart, scand;            // per block: its row, its run of scand, the sorted candidates
+    DevBuf k0, k1, v0, head, incl, temp;   // the build's scratch
+    long long n_alloc = 0, n_build = 0;
+    std::vector<DevBuf*> bufs() {
+        return {&rowptr, &col, &val, &brow, &bstart, &scand, &k0, &k1, &v0, &head, &incl, &temp};
+    }
+};
+
+namespace {
+// what every call that reads fg's plan checks first
+int fj_plan_ok(const char* who, ibtk_le_ctx ctx, ibtk_le_forcegen fg) {
+    if (!ctx) return fail(IBTK_LE_ERR_ARG, "%s: null context", who);
+    if (!fg) return fail(IBTK_LE_ERR_ARG, "%s: null force generator", who);
+    if (ctx->device != fg->ctx->device)
+        return fail(IBTK_LE_ERR_ARG, "%s: the plan lives on device %d, the context on %d", who, fg->ctx->device,
+                    ctx->device);
+    if (!fg->valid) return fail(IBTK_LE_ERR_ARG, "%s: the plan is invalid: the last forcegen_renumber failed", who);
+    return IBTK_LE_OK;
+}
+
+ForceJacPlan fj_plan(ibtk_le_forcegen fg) {
+    ForceJacPlan p{};
+    p.n = fg->n;
+    p.soff = fg->ns ? fg->soff.as<long long>() : nullptr;
+    p.boff = fg->nb ? fg->boff.as<long long>() : nullptr;
+    p.toff = fg->nt ? fg->toff.as<long long>() : nullptr;
+    p.srec = fg->srec.as<FgSpring>();
+    p.brec = fg->brec.p;
+    p.trec = fg->trec.p;
+    return p;
+}
+
+// a buffer of J at least `bytes` long; growing waits for what still reads the old block (s is
+// J's context's stream, the only one J's work runs on)
+int fj_grow(ibtk_le_forcejac J, hipStream_t s, DevBuf& b, size_t bytes) {
+    if (bytes <= b.cap) return IBTK_LE_OK;
+    HIP_TRY(hipStreamSynchronize(s));
+    ++J->n_alloc;
+    return b.ensure(bytes);
+}
+
+// the pattern of fg's current plan: everything on ctx's stream, one small read of the block
+// count in the middle (the arrays it sizes are allocated on the first build only)
+int fj_build(ibtk_le_ctx ctx, ibtk_le_forcejac J) {
+    ibtk_le_forcegen fg = J->fg;
+    if (int rc = fj_plan_ok("forcejac_rebuild", ctx, fg)) return rc;
+    if (ctx != J->ctx) return fail(IBTK_LE_ERR_ARG, "forcejac_rebuild: the Jacobian belongs to another context");
+    const long long C = (long long)fg->n + 2 * fg->ns + 9 * fg->nb;
+    if (C > INT_MAX)
+        return fail(IBTK_LE_ERR_RANGE, "forcejac_rebuild: %lld candidate blocks (nodes + 2 springs + 9 beams) exceed 2^31 - 1",
+                    C);
+    J->gen = -1;
+    J->assembled = false;
+    J->nnzb = 0;
+    J->ncand = C;
+    if (fg->n == 0) {
+        J->gen = fg->gen;
+        ++J->n_build;
+        return IBTK_LE_OK;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const int n = fg->n, c = (int)C;
+    if (int rc = fj_grow(J, s, J->rowptr, sizeof(long long) * ((size_t)n + 1))) return rc;
+    for (DevBuf* b : {&J->k0, &J->k1})
+        if (int rc = fj_grow(J, s, *b, sizeof(unsigned long long) * (size_t)c)) return rc;
+    for (DevBuf* b : {&J->v0, &J->scand, &J->head, &J->incl})
+        if (int rc = fj_grow(J, s, *b, sizeof(int) * (size_t)c)) return rc;
+    int bits = 1;  // of the row index
+    while (bits < 32 && (1ULL << bits) < (unsigned long long)n) ++bits;
+    size_t tb_sort = 0, tb_scan = 0;
+    unsigned long long *k0 = J->k0.as<unsigned long long>(), *k1 = J->k1.as<unsigned long long>();
+    int *v0 = J->v0.as<int>(), *v1 = J->scand.as<int>(), *head = J->head.as<int>(), *incl = J->incl.as<int>();
+    HIP_TRY(launch_fj_sort(nullptr, tb_sort, k0, k1, v0, v1, c, 32 + bits, s));
+    HIP_TRY(launch_fj_scan(nullptr, tb_scan, head, incl, c, s));
+    if (int rc = fj_grow(J, s, J->temp, std::max<size_t>(std::max(tb_sort, tb_scan), 8))) return rc;
+    const ForceJacPlan plan = fj_plan(fg);
+    HIP_TRY(launch_fj_keys(fg->ndim, plan, k0, v0, s));
+    size_t tb = J->temp.cap;
+    // The sort must be STABLE, as rocPRIM's radix_sort_pairs is (and as the plan rebuild of
+    // ibtk_le_forcegen_renumber needs it too): equal (row, col) keys keep the ascending order of
+    // their candidate indices, which is the order of the reference's calls.  The assembly takes a
+    // block's run in that order, and knows a diagonal block by the row's first candidate heading it.
+    HIP_TRY(launch_fj_sort(J->temp.p, tb, k0, k1, v0, v1, c, 32 + bits, s));
+    HIP_TRY(launch_fj_heads(k1, c, head, s));
+    tb = J->temp.cap;
+    HIP_TRY(launch_fj_scan(J->temp.p, tb, head, incl, c, s));
+    int nnzb = 0;
+    HIP_TRY(hipMemcpyAsync(&nnzb, incl + (c - 1), sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (nnzb < n || nnzb > c)
+        return fail(IBTK_LE_ERR_DEVICE, "forcejac_rebuild: %d blocks from %d candidates over %d rows", nnzb, c, n);
+    const size_t bs = (size_t)fg->ndim * fg->ndim;
+    if (int rc = fj_grow(J, s, J->col, sizeof(int) * (size_t)nnzb)) return rc;
+    if (int rc = fj_grow(J, s, J->val, sizeof(double) * bs * (size_t)nnzb)) return rc;
+    if (int rc = fj_grow(J, s, J->brow, sizeof(int) * (size_t)nnzb)) return rc;
+    if (int rc = fj_grow(J, s, J->bstart, sizeof(int) * ((size_t)nnzb + 1))) return rc;
+    HIP_TRY(launch_fj_scatter(k1, incl, c, n, J->rowptr.as<long long>(), J->col.as<int>(), J->brow.as<int>(),
+                              J->bstart.as<int>(), s));
+    J->nnzb = nnzb;
+    J->gen = fg->gen;
+    ++J->n_build;
+    return IBTK_LE_OK;
+}
+
+// J's pattern is that of fg's current plan
+int fj_current(const char* who, ibtk_le_ctx ctx, ibtk_le_forcejac J) {
+    if (!ctx) return fail(IBTK_LE_ERR_ARG, "%s: null context", who);
+    if (!J) return fail(IBTK_LE_ERR_ARG, "%s: null Jacobian", who);
+    if (ctx != J->ctx) return fail(IBTK_LE_ERR_ARG, "%s: the Jacobian belongs to another context", who);
+    if (!J->fg->valid) return fail(IBTK_LE_ERR_ARG, "%s: the plan is invalid: the last forcegen_renumber failed", who);
+    if (J->gen != J->fg->gen)
+        return fail(IBTK_LE_ERR_ARG,
+                    "%s: the pattern is stale: the force generator's plan has changed since it was built; call "
+                    "ibtk_le_forcejac_rebuild",
+                    who);
+    return IBTK_LE_OK;
+}
+}  // namespace
+
+extern "C" int ibtk_le_forcejac_create(ibtk_le_ctx ctx, ibtk_le_forcegen fg, ibtk_le_forcejac* out) {
+    if (!out) return fail(IBTK_LE_ERR_ARG, "forcejac_create: null out");
+    if (int rc = fj_plan_ok("forcejac_create", ctx, fg)) return rc;
+    // the pattern is rebuilt and the values assembled in the order of one stream: the plan's
+    if (fg->ctx != ctx) return fail(IBTK_LE_ERR_ARG, "forcejac_create: the force generator belongs to another context");
+    auto* J = new ibtk_le_forcejac_s();
+    J->ctx = ctx;
+    J->fg = fg;
+    if (int rc = fj_build(ctx, J)) {
+        for (DevBuf* b : J->bufs()) b->release();
+        delete J;
+        return rc;
+    }
+    *out = J;
+    return IBTK_LE_OK;
+}
+
+extern "C" int ibtk_le_forcejac_destroy(ibtk_le_forcejac J) {
+    if (!J) return IBTK_LE_OK;
+    hipSetDevice(J->ctx->device);
+    hipStreamSynchronize(J->ctx->stream);
+    for (DevBuf* b : J->bufs()) b->release();
+    delete J;
+    return IBTK_LE_OK;
+}
+
+extern "C" int ibtk_le_forcejac_rebuild(ibtk_le_ctx ctx, ibtk_le_forcejac J) {
+    if (!ctx) return fail(IBTK_LE_ERR_ARG, "forcejac_rebuild: null context");
+    if (!J) return fail(IBTK_LE_ERR_ARG, "forcejac_rebuild: null Jacobian");
+    return fj_build(ctx, J);
+}
+
+extern "C" int ibtk_le_forcejac_assemble(ibtk_le_ctx ctx, ibtk_le_forcejac J, const double* X_dev,
+                                         const double* dX_dev, double X_coef, double U_coef) {
+    if (int rc = fj_current("forcejac_assemble", ctx, J)) return rc;
+    ibtk_le_forcegen fg = J->fg;
+    if (fg->n == 0) return IBTK_LE_OK;
+    if (!X_dev) return fail(IBTK_LE_ERR_ARG, "forcejac_assemble: null array");
+    HIP_TRY(hipSetDevice(ctx->device));
+    ForceJacParams p{};
+    p.plan = fj_plan(fg);
+    p.X = X_dev;
+    p.dX = dX_dev;
+    p.X_coef = X_coef;
+    p.U_coef = U_coef;
+    p.nblocks = J->nnzb;
+    p.brow = J->brow.as<int>();
+    p.bstart = J->bstart.as<int>();
+    p.scand = J->scand.as<int>();
+    p.val = J->val.as<double>();
+    HIP_TRY(launch_forcejac_assemble(fg->ndim, p, ctx->stream));
+    J->assembled = true;
+    return IBTK_LE_OK;
+}
+
+extern "C" int ibtk_le_forcejac_apply(ibtk_le_ctx ctx, ibtk_le_forcejac J, const double* V_dev, double* Y_dev,
+                                      int accumulate) {
+    if (int rc = fj_current("forcejac_apply", ctx, J)) return rc;
+    if (!J->assembled) return fail(IBTK_LE_ERR_ARG, "forcejac_apply: no values: call ibtk_le_forcejac_assemble first");
+    if (J->fg->n == 0) return IBTK_LE_OK;
+    if (!V_dev || !Y_dev) return fail(IBTK_LE_ERR_ARG, "forcejac_apply: null array");
+    HIP_TRY(hipSetDevice(ctx->device));
+    ForceJacApplyParams p{};
+    p.n = J->fg->n;
+    p.rowptr = J->rowptr.as<long long>();
+    p.col = J->col.as<int>();
+    p.val = J->val.as<double>();
+    p.V = V_dev;
+    p.Y = Y_dev;
+    p.accumulate = accumulate ? 1 : 0;
+    HIP_TRY(launch_forcejac_apply(J->fg->ndim, p, ctx->stream));
+    return IBTK_LE_OK;
+}
+
+extern "C" int ibtk_le_forcejac_pattern(ibtk_le_forcejac J, long long* n_blocks, const long long** rowptr_dev,
+                                        const int** col_dev, double** val_dev) {
+    if (!J) return fail(IBTK_LE_ERR_ARG, "forcejac_pattern: null Jacobian");
+    if (J->gen < 0) return fail(IBTK_LE_ERR_ARG, "forcejac_pattern: no pattern: the last forcejac_rebuild failed");
+    if (n_blocks) *n_blocks = J->nnzb;
+    if (rowptr_dev) *rowptr_dev = J->rowptr.as<long long>();
+    if (col_dev) *col_dev = J->col.as<int>();
+    if (val_dev) *val_dev = J->val.as<double>();
+    return IBTK_LE_OK;
+}
+
+extern "C" int ibtk_le_forcejac_read(ibtk_le_forcejac J, long long* rowptr_host, int* col_host, double* val_host,
+                                     long long n_blocks) {
+    if (!J) return fail(IBTK_LE_ERR_ARG, "forcejac_read: null Jacobian");
+    if (J->gen < 0) return fail(IBTK_LE_ERR_ARG, "forcejac_read: no pattern: the last forcejac_rebuild failed");
+    if (n_blocks != J->nnzb)
+        return fail(IBTK_LE_ERR_ARG, "forcejac_read: n_blocks %lld, the pattern holds %lld", n_blocks, J->nnzb);
+    if (!rowptr_host) return fail(IBTK_LE_ERR_ARG, "forcejac_read: null rowptr");
+    if (J->nnzb > 0 && !col_host) return fail(IBTK_LE_ERR_ARG, "forcejac_read: null col");
+    if (J->fg->n == 0) {
+        rowptr_host[0] = 0;
+        return IBTK_LE_OK;
+    }
+    HIP_TRY(hipSetDevice(J->ctx->device));
+    HIP_TRY(hipStreamSynchronize(J->ctx->stream));
+    HIP_TRY(hipMemcpy(rowptr_host, J->rowptr.p, sizeof(long long) * ((size_t)J->fg->n + 1), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(col_host, J->col.p, sizeof(int) * (size_t)J->nnzb, hipMemcpyDeviceToHost));
+    if (val_host) {
+        if (!J->assembled) return fail(IBTK_LE_ERR_ARG, "forcejac_read: no values: call ibtk_le_forcejac_assemble first");
+        const size_t bs = (size_t)J->fg->ndim * J->fg->ndim;
+        HIP_TRY(hipMemcpy(val_host, J->val.p, sizeof(double) * bs * (size_t)J->nnzb, hipMemcpyDeviceToHost));
+    }
+    return IBTK_LE_OK;
+}
+
+extern "C" int ibtk_le_forcejac_stats(ibtk_le_forcejac J, long long* out) {
+    if (!J || !out) return fail(IBTK_LE_ERR_ARG, "forcejac_stats: null argument");
+    out[0] = J->nnzb;
+    out[1] = J->ncand;
+    size_t bytes = 0;
+    for (DevBuf* b : J->bufs()) bytes += b->cap;
+    out[2] = (long long)bytes;
+    out[3] = J->n_alloc;
+    out[4] = J->n_build;
+    out[5] = J->gen == J->fg->gen ? 1 : 0;
+    return IBTK_LE_OK;
+}
+
+extern "C" int ibtk_le_forcegen_linearized(ibtk_le_ctx ctx, ibtk_le_forcegen fg, const double* X_dev,
+                                           const double* dX_dev, const double* V_dev, double X_coef, double U_coef,
+                                           double* Y_dev, int accumulate) {
+    if (int rc = fj_plan_ok("forcegen_linearized", ctx, fg)) return rc;
+    if (fg->n == 0) return IBTK_LE_OK;
+    if (!X_dev || !V_dev || !Y_dev) return fail(IBTK_LE_ERR_ARG, "forcegen_linearized: null array");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (fg->ns == 0 && fg->nb == 0 && fg->nt == 0) {
+        if (!accumulate) HIP_TRY(hipMemsetAsync(Y_dev, 0, sizeof(double) * (size_t)fg->n * fg->ndim, ctx->stream));
+        return IBTK_LE_OK;
+    }
+    ForceJacParams p{};
+    p.plan = fj_plan(fg);
+    p.X = X_dev;
+    p.dX = dX_dev;
+    p.X_coef = X_coef;
+    p.U_coef = U_coef;
+    HIP_TRY(launch_forcegen_linearized(fg->ndim, p, V_dev, Y_dev, accumulate ? 1 : 0, ctx->stream));
+    return IBTK_LE_OK;
+}
+
+extern "C" int ibtk_le_forcegen_jacobian_nnz(ibtk_le_ctx ctx, ibtk_le_forcegen fg, int n_local, int* d_nnz_dev,
+                                             int* o_nnz_dev) {
+    if (int rc = fj_plan_ok("forcegen_jacobian_nnz", ctx, fg)) return rc;
+    if (n_local < 0 || n_local > fg->n)
+        return fail(IBTK_LE_ERR_ARG, "forcegen_jacobian_nnz: n_local %d is outside [0, %d], the plan's nodes", n_local,
+                    fg->n);
+    if (fg->n == 0) return IBTK_LE_OK;
+    if (!d_nnz_dev || !o_nnz_dev) return fail(IBTK_LE_ERR_ARG, "forcegen_jacobian_nnz: null array");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(launch_forcegen_nnz(fg->ndim, fj_plan(fg), n_local, d_nnz_dev, o_nnz_dev, ctx->stream));
     return IBTK_LE_OK;
 }
 

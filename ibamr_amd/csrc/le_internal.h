@@ -328,6 +328,49 @@ struct ForceGenParams {
     int accumulate;                        // F = F + acc, else F = acc
 };
 hipError_t launch_forcegen(int ndim, const ForceGenParams& p, hipStream_t s);
+// The force Jacobian read from the same plan (le_force_jac.hip, ibtk_le_forcejac).  Row i's
+// candidate blocks sit at cand(i) = i + soff[i] + 3 boff[i]: the diagonal, one per spring
+// entry, three per beam entry (prev, next, master).  Block b of row brow[b] takes the
+// candidates scand[bstart[b] .. bstart[b + 1]), in that order.
+struct ForceJacPlan {
+    long n;                                // nodes = block rows
+    const long long *soff, *boff, *toff;   // as ForceGenParams; NULL: no such entries
+    const FgSpring* srec;
+    const void* brec;
+    const void* trec;
+};
+struct ForceJacParams {
+    ForceJacPlan plan;
+    const double *X, *dX;                  // dX may be NULL
+    double X_coef, U_coef;
+    // assembly only
+    long long nblocks;
+    const int *brow, *bstart, *scand;      // nblocks, nblocks + 1, one per candidate
+    double* val;                           // nblocks blocks of ndim^2 doubles, row-major
+};
+struct ForceJacApplyParams {
+    long n;
+    const long long* rowptr;               // n + 1
+    const int* col;
+    const double *val, *V;
+    double* Y;
+    int accumulate;                        // Y = Y + J V, else Y = J V
+};
+// symbolic phase: the (row << 32 | col) key and the index of every candidate; a 64-bit radix
+// sort; head[j] = sorted key j differs from key j - 1; an inclusive scan of the heads;
+// rowptr, col, brow and bstart from the scan (rowptr[n] = the block count, bstart[that] = C)
+hipError_t launch_fj_keys(int ndim, const ForceJacPlan& p, unsigned long long* keys, int* vals, hipStream_t s);
+hipError_t launch_fj_sort(void* temp, size_t& temp_bytes, const unsigned long long* kin, unsigned long long* kout,
+                          const int* vin, int* vout, int n, int end_bit, hipStream_t s);
+hipError_t launch_fj_heads(const unsigned long long* skeys, int C, int* head, hipStream_t s);
+hipError_t launch_fj_scan(void* temp, size_t& temp_bytes, const int* in, int* out, int n, hipStream_t s);
+hipError_t launch_fj_scatter(const unsigned long long* skeys, const int* incl, int C, long n, long long* rowptr,
+                             int* col, int* brow, int* bstart, hipStream_t s);
+hipError_t launch_forcejac_assemble(int ndim, const ForceJacParams& p, hipStream_t s);
+hipError_t launch_forcejac_apply(int ndim, const ForceJacApplyParams& p, hipStream_t s);
+hipError_t launch_forcegen_linearized(int ndim, const ForceJacParams& p, const double* V, double* Y, int accumulate,
+                                      hipStream_t s);
+hipError_t launch_forcegen_nnz(int ndim, const ForceJacPlan& p, int n_local, int* d_nnz, int* o_nnz, hipStream_t s);
 // The plan rebuilt on the device for a new numbering (le_force_plan.hip,
 // ibtk_le_forcegen_renumber).  The spec store holds the same records in deck order with
 // Lagrangian vertex indices (beams with role 0; target points beside an int array of their

@@ -18,6 +18,12 @@ position update and the spread.  Three pieces live here:
 * :class:`DeviceForceSpecs` -- the specs on the device in Lagrangian indices
   (``ibtk_le_forcespecs``), from which :meth:`ForceGen.renumber` rebuilds the plan on the
   device whenever a regrid renumbers the nodes.
+
+* :class:`ForceJacobian` -- the other half of the strategy,
+  ``computeLagrangianForceJacobian`` (``:498-665``): ``dF/dX`` in block-CSR on the device
+  (``ibtk_le_forcejac``), its pattern built from the plan, its values bit for bit the serial
+  assembly, and the product ``J V``; beside it :meth:`ForceGen.linearized` (the product
+  without a matrix) and :meth:`ForceGen.jacobian_nnz` (the preallocation counts).
 """
 from __future__ import annotations
 
@@ -31,7 +37,7 @@ import numpy as np
 from . import _lib, io
 from ._lib import check
 
-__all__ = ["SpringArrays", "BeamArrays", "TargetArrays", "ForceSpecs", "ForceGen", "DeviceForceSpecs"]
+__all__ = ["SpringArrays", "BeamArrays", "TargetArrays", "ForceSpecs", "ForceGen", "ForceJacobian", "DeviceForceSpecs"]
 
 
 class SpringArrays(NamedTuple):
@@ -331,6 +337,43 @@ class ForceGen:
         check(self.lib.ibtk_le_forcegen_renumber_stats(self.h, out))
         return {"kept": tuple(out[0:3]), "dropped": tuple(out[3:6]), "bytes": out[6], "allocations": out[7]}
 
+    def linearized(self, X, V, Y=None, dX=None, X_coef: float = 1.0, U_coef: float = 0.0, accumulate: bool = False):
+        """``Y += J V`` (``accumulate``) or ``Y = J V`` with ``J`` the force Jacobian at
+        ``X + dX`` (:class:`ForceJacobian`'s matrix), formed and applied contribution by
+        contribution straight from the plan: the exact product in place of the
+        finite-difference ``compute(dX=...)`` route.  ``[n_nodes][ndim]`` float64 device
+        tensors; ``Y=None`` allocates the result.  Returns ``Y``.  No host synchronisation."""
+        import torch
+
+        from .le import _ptr
+        shape = (self.n_nodes, self.ndim)
+        if Y is None:
+            Y = torch.empty(shape, dtype=torch.float64, device=X.device)
+            accumulate = False
+        for name, t in (("X", X), ("V", V), ("Y", Y), ("dX", dX)):
+            if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous float64 tensor of shape {shape}")
+        check(self.lib.ibtk_le_forcegen_linearized(self.ctx.h, self.h, _ptr(X), _ptr(dX), _ptr(V), float(X_coef),
+                                                   float(U_coef), _ptr(Y), int(bool(accumulate))))
+        return Y
+
+    def jacobian_nnz(self, n_local: Optional[int] = None, device=None):
+        """The preallocation counts of ``computeLagrangianForceJacobianNonzeroStructure`` per
+        block row: ``(d_nnz, o_nnz)``, two ``n_nodes`` int32 device tensors.  Nodes with an
+        index below ``n_local`` (default: all) are local, the others trailing ghost nodes.
+        No host synchronisation."""
+        import torch
+
+        from .le import _ptr
+        n_local = self.n_nodes if n_local is None else int(n_local)
+        if not 0 <= n_local <= self.n_nodes:
+            raise ValueError(f"n_local {n_local} is outside [0, {self.n_nodes}]")
+        dev = torch.device("cuda", self.ctx.device) if device is None else device
+        d = torch.empty(self.n_nodes, dtype=torch.int32, device=dev)
+        o = torch.empty(self.n_nodes, dtype=torch.int32, device=dev)
+        check(self.lib.ibtk_le_forcegen_jacobian_nnz(self.ctx.h, self.h, n_local, _ptr(d), _ptr(o)))
+        return d, o
+
     def record_dtype(self, cls: int) -> np.dtype:
         """The structured dtype of class ``cls``'s plan records (0 springs, 1 beams, 2 target
         points); no padding."""
@@ -355,6 +398,142 @@ class ForceGen:
     def close(self):
         if getattr(self, "h", None) and getattr(self.ctx, "h", None):
             self.lib.ibtk_le_forcegen_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        if sys.is_finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _DeviceArray:
+    """A device array of the library's as ``__cuda_array_interface__``: what
+    ``torch.as_tensor`` wraps without copying.  It keeps its owner alive."""
+
+    def __init__(self, owner, ptr: int, shape, typestr: str):
+        self.owner = owner
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr or 0), False),
+                                         "version": 2, "strides": None}
+
+
+class ForceJacobian:
+    """The force Jacobian ``dF/dX`` of a :class:`ForceGen` on the device, in block-CSR
+    (``ibtk_le_forcejac``): what ``IBStandardForceGen::computeLagrangianForceJacobian``
+    (``src/IB/IBStandardForceGen.cpp:498-665``) assembles, bit for bit.
+
+    The pattern is built here, on the device, from ``fg``'s current plan; after a ``fg.set_*``
+    or ``fg.renumber`` it is stale -- :meth:`assemble` and :meth:`apply` raise ``IBTKLEError``
+    -- until :meth:`rebuild`.  ``ctx`` must be the context ``fg`` was created with.  Only the
+    (re)build's last step and :meth:`read` synchronise with the host."""
+
+    def __init__(self, ctx, fg: ForceGen):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        self.fg = fg  # the library reads fg's plan on every assemble: keep it alive
+        self.n_nodes = fg.n_nodes
+        self.ndim = fg.ndim
+        h = ctypes.c_void_p()
+        check(self.lib.ibtk_le_forcejac_create(ctx.h, fg.h, ctypes.byref(h)))
+        self.h = h
+
+    def _live(self):
+        """The handle, for a call into the library: the library reads ``fg``'s plan through the
+        Jacobian, so neither may have been closed."""
+        if getattr(self, "h", None) is None:
+            raise ValueError("the ForceJacobian is closed")
+        if getattr(self.fg, "h", None) is None:
+            raise ValueError("the ForceGen this ForceJacobian was built from is closed")
+        return self.h
+
+    def rebuild(self) -> dict:
+        """Build the pattern again from ``fg``'s current plan.  Over a plan with the same counts
+        nothing is allocated.  Views from an earlier :meth:`bsr` are invalid afterwards.
+        Returns :meth:`stats`."""
+        check(self.lib.ibtk_le_forcejac_rebuild(self.ctx.h, self._live()))
+        return self.stats()
+
+    def _check(self, **tensors):
+        import torch
+        shape = (self.n_nodes, self.ndim)
+        for name, t in tensors.items():
+            if t is not None and (t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous float64 tensor of shape {shape}")
+
+    def assemble(self, X, dX=None, X_coef: float = 1.0, U_coef: float = 0.0) -> "ForceJacobian":
+        """The values at ``X + dX``: every block from ``+0.0``, the contributions added as whole
+        blocks in the reference's call order.  No host synchronisation."""
+        from .le import _ptr
+        self._check(X=X, dX=dX)
+        check(self.lib.ibtk_le_forcejac_assemble(self.ctx.h, self._live(), _ptr(X), _ptr(dX), float(X_coef), float(U_coef)))
+        return self
+
+    def apply(self, V, Y=None, accumulate: bool = False):
+        """``Y += J V`` (``accumulate``) or ``Y = J V``; ``Y=None`` allocates the result.  The
+        summation order is fixed: identical bits run to run.  Returns ``Y``."""
+        import torch
+
+        from .le import _ptr
+        if Y is None:
+            Y = torch.empty((self.n_nodes, self.ndim), dtype=torch.float64, device=V.device)
+            accumulate = False
+        self._check(V=V, Y=Y)
+        check(self.lib.ibtk_le_forcejac_apply(self.ctx.h, self._live(), _ptr(V), _ptr(Y), int(bool(accumulate))))
+        return Y
+
+    def _pattern(self):
+        nb = ctypes.c_longlong()
+        rp, cl, vl = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        check(self.lib.ibtk_le_forcejac_pattern(self._live(), ctypes.byref(nb), ctypes.byref(rp), ctypes.byref(cl),
+                                                ctypes.byref(vl)))
+        return nb.value, rp.value, cl.value, vl.value
+
+    @property
+    def n_blocks(self) -> int:
+        return self._pattern()[0]
+
+    def bsr(self):
+        """``(rowptr, col, val)`` as torch views of the library's device arrays, no copy:
+        ``n_nodes + 1`` int64, ``n_blocks`` int32 ascending within a row, ``(n_blocks, ndim,
+        ndim)`` float64 row-major blocks.  Valid until the next :meth:`rebuild`; reads are
+        ordered after :meth:`assemble` on the context's stream."""
+        import torch
+        nb, rp, cl, vl = self._pattern()
+        dev = torch.device("cuda", self.ctx.device)
+        if self.n_nodes == 0 or nb == 0:
+            return (torch.zeros(self.n_nodes + 1, dtype=torch.int64, device=dev),
+                    torch.empty(0, dtype=torch.int32, device=dev),
+                    torch.empty((0, self.ndim, self.ndim), dtype=torch.float64, device=dev))
+        return (torch.as_tensor(_DeviceArray(self, rp, (self.n_nodes + 1,), "<i8"), device=dev),
+                torch.as_tensor(_DeviceArray(self, cl, (nb,), "<i4"), device=dev),
+                torch.as_tensor(_DeviceArray(self, vl, (nb, self.ndim, self.ndim), "<f8"), device=dev))
+
+    def read(self, values: bool = True):
+        """``(rowptr, col, val)`` as numpy arrays (blocking; tests and debugging);
+        ``values=False`` reads the pattern alone and returns ``val = None``."""
+        nb = self._pattern()[0]
+        rowptr = np.zeros(self.n_nodes + 1, dtype=np.int64)
+        col = np.empty(nb, dtype=np.int32)
+        val = np.empty((nb, self.ndim, self.ndim), dtype=np.float64) if values else None
+        check(self.lib.ibtk_le_forcejac_read(self._live(), _host_ptr(rowptr), _host_ptr(col), _host_ptr(val), nb))
+        return rowptr, col, val
+
+    def stats(self) -> dict:
+        """``blocks``, ``candidates`` (nodes + 2 springs + 9 beams), the device ``bytes`` held,
+        the device ``allocations`` and ``builds`` so far, and whether the pattern is
+        ``current``."""
+        out = (ctypes.c_longlong * 6)()
+        check(self.lib.ibtk_le_forcejac_stats(self._live(), out))
+        return {"blocks": out[0], "candidates": out[1], "bytes": out[2], "allocations": out[3], "builds": out[4],
+                "current": bool(out[5])}
+
+    def close(self):
+        # destroy frees the Jacobian's own buffers and never looks at fg: it runs whether or not
+        # fg was closed first
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.lib.ibtk_le_forcejac_destroy(self.h)
         self.h = None
 
     def __del__(self):

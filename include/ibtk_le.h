@@ -673,6 +673,107 @@ int ibtk_le_forcegen_plan_size(ibtk_le_forcegen fg, int cls, long long* n_entrie
 int ibtk_le_forcegen_plan_read(ibtk_le_forcegen fg, int cls, long long* off_host, void* rec_host,
                                long long rec_bytes);
 
+/* ---- The force Jacobian (the other half of IBLagrangianForceStrategy) -----------------
+ * IBStandardForceGen::computeLagrangianForceJacobian (IBStandardForceGen.cpp:498-665) adds,
+ * with MatSetValuesBlocked(ADD_VALUES), NDIM x NDIM blocks into a matrix over the nodes, in
+ * three serial loops over k.  At positions x = X + dX, with the caller's X_coef and U_coef:
+ *   spring k (m, s, kappa, L): D = x[s] - x[m]; R = D.norm(), Eigen 3.2.1's unrolled
+ *     reduction sqrt(D0^2 + (D1^2 + D2^2)) in 3-D (Redux.h:77-106; not the force loop's
+ *     left-to-right sum), sqrt(D0^2 + D1^2) in 2-D; T = kappa (R - L), dT_dR = kappa (the
+ *     default law and its derivative, IBSpringForceFunctions.h:117-131);
+ *       dF(i, j) = X_coef ((T / R) delta_ij + (((dT_dR - T / R) D[i]) D[j]) / (R R)).
+ *     dF.data() is column-major and MatSetValuesBlocked reads it row-major, so the STORED
+ *     element (r, c) of the block is dF(c, r) -- the two differ in the last bit, (a D[i]) D[j]
+ *     does not commute under rounding.  Blocks (m, s) and (s, m) += dF; (m, m) and (s, s) +=
+ *     dF * -1.0.  There is no guard for R = 0: a spring between coincident nodes puts NaN
+ *     (0 / 0) into its four blocks, (m, s), (s, m), (m, m), (s, s), and nowhere else.
+ *   beam k (m, next n, prev p, bend): diagonal blocks, the zeros off their diagonals added
+ *     like every other element: (p,p) (p,n) (n,p) (n,n) += (-1.0 bend) X_coef; (p,m) (n,m)
+ *     (m,p) (m,n) += (2.0 bend) X_coef; (m,m) += (-4.0 bend) X_coef.
+ *   target point k (node i, K, E): (i,i) += diagonal ((-X_coef) K) - (U_coef E).
+ *
+ * ibtk_le_forcejac is that matrix on the device in block-CSR over the n_nodes of a force
+ * generator: rowptr[n_nodes + 1] int64, col[n_blocks] int32 ascending within a row,
+ * val[n_blocks][ndim][ndim] float64, row-major blocks.  The pattern is exactly the set of
+ * blocks those calls touch plus the diagonal block of every node (which the reference
+ * preallocates, :351); repeated entries -- a repeated edge, a spring and a beam between
+ * the same nodes, a beam with next == prev -- are one block.
+ *
+ * create builds the pattern on the device from fg's CURRENT plan (a 64-bit radix sort of
+ * the (row, col) keys of every plan entry, a scan; no host trip but one small read of the
+ * block count, which blocks) and, per block, the plan entries that contribute to it in the
+ * reference's order, so that assemble searches nothing.  ctx must be the context fg was
+ * created with.  rebuild does it again
+ * after fg was changed by a set_* or a renumber: every such call advances fg's plan
+ * generation, and assemble and apply return IBTK_LE_ERR_ARG ("the pattern is stale ...
+ * call ibtk_le_forcejac_rebuild") while J's pattern is of an older generation.  A plan left
+ * invalid by a failed renumber is refused as ibtk_le_forcegen_compute refuses it.  The
+ * arrays and the scratch are sized on the first build; a rebuild over a plan with the same
+ * counts (nodes, springs, beams, blocks) allocates nothing.  More than 2^31 - 1 candidate
+ * blocks (n_nodes + 2 springs + 9 beams): IBTK_LE_ERR_RANGE.  fg must outlive J.
+ *
+ * Contexts.  Every ibtk_le_forcejac_* call that takes a ctx wants the ONE context fg was
+ * created with (another: IBTK_LE_ERR_ARG, "another context"): J's arrays are written by
+ * rebuild and assemble and read by apply in the order of that context's stream, and nothing
+ * else orders them.  ibtk_le_forcegen_linearized and ibtk_le_forcegen_jacobian_nnz below
+ * only READ the plan, as ibtk_le_forcegen_compute does, and follow its rule: any context on
+ * the plan's device (another device: IBTK_LE_ERR_ARG).  That is safe because whatever
+ * changes a plan -- a set_* or a renumber -- returns only after the plan is in place. */
+typedef struct ibtk_le_forcejac_s* ibtk_le_forcejac;
+int ibtk_le_forcejac_create(ibtk_le_ctx ctx, ibtk_le_forcegen fg, ibtk_le_forcejac* out);
+int ibtk_le_forcejac_destroy(ibtk_le_forcejac J);
+int ibtk_le_forcejac_rebuild(ibtk_le_ctx ctx, ibtk_le_forcejac J);
+/* val = the Jacobian at X + dX ([n_nodes][ndim] device arrays; dX_dev may be NULL; one
+ * rounded add per use).  Every block starts at +0.0, as after MatZeroEntries, and takes its
+ * contributions as whole blocks in the order of the reference's calls: springs ascending
+ * in k, then beams ascending in k, then target points.  One lane owns each block: it sums
+ * the block's contributions in registers, in the order the pattern build recorded for it
+ * (the block's run of the row's plan entries; on a diagonal block the row's springs first,
+ * the row's target points last), and stores the block once.  No floating-point atomics, the
+ * same bits run to run, and bit for bit the serial assembly (signed zeros included; NaN for
+ * coincident spring nodes, see above).  One rounded operation per reference operation, IEEE
+ * sqrt and divide.  Ordered on ctx's stream, no host synchronisation, no allocation. */
+int ibtk_le_forcejac_assemble(ibtk_le_ctx ctx, ibtk_le_forcejac J, const double* X_dev, const double* dX_dev,
+                              double X_coef, double U_coef);
+/* Y = Y + J V (accumulate != 0) or Y = J V with the assembled values; V and Y are
+ * [n_nodes][ndim] float64 device arrays (8-byte alignment suffices), Y must not alias V.
+ * The summation order is fixed by the pattern, so the result has the same bits run to run:
+ * the doubles of block row i, in storage order, are numbered e = 0, 1, ...; with b = e /
+ * ndim^2, r = (e % ndim^2) / ndim and c = e % ndim, lane l of 16 adds the products val[e]
+ * V[col[b]][c] for e = l, l + 16, l + 32, ... in that order to its partial sum of
+ * component r (from +0.0), and the 16 partial sums of a component are combined pairwise
+ * at lane distances 8, 4, 2, 1.  No host synchronisation, no allocation. */
+int ibtk_le_forcejac_apply(ibtk_le_ctx ctx, ibtk_le_forcejac J, const double* V_dev, double* Y_dev, int accumulate);
+/* The block count and the DEVICE pointers of rowptr, col and val (any may be NULL), to wrap
+ * or to copy into a block AIJ matrix; they stay valid until the next rebuild or destroy. */
+int ibtk_le_forcejac_pattern(ibtk_le_forcejac J, long long* n_blocks, const long long** rowptr_dev,
+                             const int** col_dev, double** val_dev);
+/* The same to the host, for tests and debugging; it blocks.  n_blocks must be the pattern's
+ * count; val_host may be NULL (pattern only), else the values must have been assembled. */
+int ibtk_le_forcejac_read(ibtk_le_forcejac J, long long* rowptr_host, int* col_host, double* val_host,
+                          long long n_blocks);
+/* out[0] blocks, out[1] candidate blocks (n_nodes + 2 springs + 9 beams), out[2] the device
+ * bytes J holds, out[3] the device allocations its builds have made so far, out[4] its
+ * builds, out[5] 1 if the pattern is of fg's current plan generation. */
+int ibtk_le_forcejac_stats(ibtk_le_forcejac J, long long* out);
+/* Y (+)= J(X + dX) V without a matrix: the exact product in place of the MatMFFD
+ * difference of IBMethod::computeLinearizedLagrangianForce (IBMethod.cpp:710-723).  The
+ * gather kernel of compute with every contribution's block formed exactly as assemble forms
+ * it and applied to V at the block's column at once -- row by row of the block, left to
+ * right -- in contribution order: a node's springs by k (the off-diagonal block, then the
+ * diagonal one), its beams by k (columns prev, next, master), its target points.  Same bits
+ * run to run.  Arguments as compute's; Y must not alias X, dX or V. */
+int ibtk_le_forcegen_linearized(ibtk_le_ctx ctx, ibtk_le_forcegen fg, const double* X_dev, const double* dX_dev,
+                                const double* V_dev, double X_coef, double U_coef, double* Y_dev, int accumulate);
+/* The per-block-row counts of computeLagrangianForceJacobianNonzeroStructure (:315-496)
+ * before its expansion to scalar rows: d_nnz = 1 and o_nnz = 0, each spring adds 1 at its
+ * master and at its slave (to d_nnz if the SLAVE is local, else to o_nnz), each beam the
+ * weights of the reference's four cases (:401-455), its deliberate over-count included.  A
+ * node is local iff its index is < n_local (0 <= n_local <= n_nodes: trailing ghost nodes).
+ * Both outputs are n_nodes int32 on the device.  No host synchronisation. */
+int ibtk_le_forcegen_jacobian_nnz(ibtk_le_ctx ctx, ibtk_le_forcegen fg, int n_local, int* d_nnz_dev,
+                                  int* o_nnz_dev);
+
 /* ---- Kirchhoff rods (IBKirchhoffRodForceGen, GeneralizedIBMethod) ---------------------
  * The Lagrangian side of the generalized IB step, 3-D and fp64: the force F and torque N
  * of IBKirchhoffRodForceGen::computeLagrangianForceAndTorque (IBKirchhoffRodForceGen.cpp:

@@ -19,8 +19,16 @@ route it replaces (ForceSpecs.arrays(perm), then ForceGen(...) through the set_*
 their upload; wall clock, --host-iters times).  The two plans are compared byte for byte
 unless --no-verify.  Default --out: profiles/forcegen_renumber.json.
 
+--jacobian measures the force Jacobian on the same sheet: the pattern build
+(ForceJacobian.rebuild, which ends in one small read), assemble, apply, ForceGen.linearized and,
+alternating with them in the same process, compute(dX=...), whose bytes linearized moves; HIP
+events, warm-up and --iters as above.  Each time stands next to its algorithmic bytes and the
+fraction of 6.29 TB/s (the achievable streaming rate) they amount to.  Default --out:
+profiles/forcejac_sheet.json.
+
 Usage: python tools/bench_forcegen.py [--n-side N] [--iters K] [--warmup W] [--out FILE]
        python tools/bench_forcegen.py --renumber [--n-side N] [--iters K] [--warmup W] [--host-iters H]
+       python tools/bench_forcegen.py --jacobian [--n-side N] [--iters K] [--warmup W] [--out FILE]
 """
 import argparse
 import json
@@ -138,6 +146,104 @@ def renumber_bench(args):
         sys.exit("bench_forcegen: the rebuilt plan differs from the host plan")
 
 
+HBM_ACHIEVABLE = 6.29e12  # bytes per second: the streaming copy rate the fractions below are of
+
+
+def jacobian_bench(args):
+    import torch
+
+    from ibamr_amd import build, le
+    from ibamr_amd.forcegen import ForceGen, ForceJacobian
+
+    if not torch.cuda.is_available():
+        sys.exit("bench_forcegen: no GPU (this measurement has no CPU fallback)")
+    N, nd = args.n_side, 3
+    n = N * N
+    rng = np.random.default_rng(0)
+    Xh, springs, beams, targets = sheet(N, rng)
+    ns, nb, nt = springs[0].size, beams[0].size, targets[0].size
+    ctx = le.Context(0)
+    fg = ForceGen(ctx, n, nd, springs=springs, beams=beams, targets=targets)
+    X = torch.from_numpy(Xh).cuda()
+    dX = torch.zeros_like(X)
+    U = torch.randn((n, nd), dtype=torch.float64, device="cuda")
+    V = torch.randn((n, nd), dtype=torch.float64, device="cuda")
+    F = torch.empty_like(X)
+    Y = torch.empty_like(X)
+    X_coef, U_coef = 0.5, -0.25 / 1.0e-3
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    J = ForceJacobian(ctx, fg)  # the first build allocates
+    build_ms = [timed(J.rebuild) for _ in range(args.warmup + args.iters)][args.warmup:]
+    stats = J.stats()
+    calls = {
+        "compute_dX": lambda: fg.compute(X, U=U, F=F, dX=dX, accumulate=False),
+        "linearized": lambda: fg.linearized(X, V, Y=Y, dX=dX, X_coef=X_coef, U_coef=U_coef),
+        "assemble": lambda: J.assemble(X, dX=dX, X_coef=X_coef, U_coef=U_coef),
+        "apply": lambda: J.apply(V, Y=Y),
+    }
+    for _ in range(args.warmup):
+        for fn in calls.values():
+            fn()
+    ctx.synchronize()
+    ms = {k: [] for k in calls}
+    for _ in range(args.iters):  # the four alternate, so that they share whatever else the device does
+        for k, fn in calls.items():
+            ms[k].append(timed(fn))
+    # the product against the linearized force, once: two summation orders of the same terms
+    Ya = J.apply(V)
+    Yl = fg.linearized(X, V, dX=dX, X_coef=X_coef, U_coef=U_coef)
+    ctx.synchronize()
+    scale = float(Yl.abs().max())
+    diff = float((Ya - Yl).abs().max())
+
+    rec = {"spring": 24, "beam": 24 + 8 * nd, "target": 16 + 8 * nd}
+    plan = 3 * 8 * (n + 1) + 2 * ns * rec["spring"] + 3 * nb * rec["beam"] + nt * rec["target"]
+    vec = n * nd * 8
+    blocks, cand = stats["blocks"], stats["candidates"]
+    bs = nd * nd * 8
+    # bytes the algorithm needs, each array once (neighbour gathers taken as cache hits):
+    #   compute(dX) / linearized: the plan, X, dX, U or V, F or Y
+    #   assemble: the plan, X, dX, the sorted candidates (an int each), a row and a run start
+    #     per block, every block written once (a spring's record is read at both its
+    #     off-diagonal blocks and at both its diagonal ones: taken as cache hits too)
+    #   apply: rowptr, col, val, V, Y
+    alg = {"compute_dX": plan + 4 * vec, "linearized": plan + 4 * vec,
+           "assemble": plan + 2 * vec + 4 * cand + (8 + bs) * blocks,
+           "apply": 8 * (n + 1) + 4 * blocks + bs * blocks + 2 * vec}
+    r4 = lambda v: round(v, 4)  # noqa: E731
+    res = {
+        "bench": "forcejac_sheet", "source_hash": build.source_hash(), "device": torch.cuda.get_device_name(0),
+        "n_side": N, "nodes": n, "springs": ns, "beams": nb, "targets": nt, "iters": args.iters,
+        "warmup": args.warmup, "blocks": blocks, "blocks_per_node": round(blocks / n, 2), "candidates": cand,
+        "device_bytes_held": stats["bytes"], "device_allocations": stats["allocations"],
+        "pattern_build_ms": {"median": r4(statistics.median(build_ms)), "min": r4(min(build_ms)),
+                             "max": r4(max(build_ms))},
+    }
+    for k in calls:
+        med = statistics.median(ms[k])
+        rate = alg[k] / (med * 1e-3)
+        res[k] = {"ms": {"median": r4(med), "min": r4(min(ms[k])), "max": r4(max(ms[k]))},
+                  "algorithmic_bytes": alg[k], "bytes_per_node": round(alg[k] / n, 1),
+                  "algorithmic_GB_per_s": round(rate / 1e9, 1),
+                  "fraction_of_6.29_TB_per_s": round(rate / HBM_ACHIEVABLE, 3)}
+    res["linearized_over_compute_dX"] = round(statistics.median(ms["linearized"])
+                                              / statistics.median(ms["compute_dX"]), 3)
+    res["apply_minus_linearized_max"] = diff
+    res["linearized_max_abs"] = scale
+    print(json.dumps(res))
+    out = Path(args.out or ROOT / "profiles" / "forcejac_sheet.json")
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(json.dumps(res, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--n-side", type=int, default=3162)
@@ -147,9 +253,13 @@ def main():
     ap.add_argument("--renumber", action="store_true", help="time the plan rebuild at a renumbering instead")
     ap.add_argument("--host-iters", type=int, default=2, help="--renumber: timed runs of the host route")
     ap.add_argument("--no-verify", action="store_true", help="--renumber: skip the byte comparison of the plans")
+    ap.add_argument("--jacobian", action="store_true",
+                    help="time the force Jacobian (pattern build, assemble, apply, linearized) beside compute(dX)")
     args = ap.parse_args()
     if args.renumber:
         return renumber_bench(args)
+    if args.jacobian:
+        return jacobian_bench(args)
 
     import torch
 
