@@ -173,14 +173,24 @@ __device__ __forceinline__ int closed_weights(double X_o_dx, int ilower, double*
     return ic_lower;
 }
 
+// a / b from inv_b = 1 / b (correctly rounded): the product, its exact residual and one
+// correction -- the correctly rounded quotient (Markstein), so the spread's X_o_dx has the
+// Fortran's bits without its division
+__device__ __forceinline__ double quotient_mul(double a, double b, double inv_b) {
+    const double q = a * inv_b;
+    return __builtin_fma(__builtin_fma(-q, b, a), inv_b, q);
+}
+
 // One dimension of one component's stencil: weights + clipped range.
 //   Xs   = X(d,s) + Xshift(d,l);  Xraw = X(d,s)
 //   xlo  = the component frame's x_lower(d);  ilo = its ilower(d)
 //   [glo, ghi] = the component array's ghost box in dim d
 //   axis_dim = (d == axis) for DISCONTINUOUS_LINEAR
-//   MUL: X_o_dx by a multiply with inv_dx = 1/dx instead of the Fortran's
-//        division (closed-form kernels only): within an ulp of it, for the
-//        spread, whose sums are compared by tolerance, not bit for bit
+//   MUL: X_o_dx from a multiply with inv_dx = 1/dx and one correction
+//        (quotient_mul) instead of the Fortran's division (closed-form kernels
+//        only, for the spread): the quotient's bits.  The bare product is an ulp
+//        of X_o_dx off, which moves a weight at the fringe of the support by
+//        1e-10 of itself (tests/test_gpu_level_shapes.py's per-point bound)
 #ifndef IBTK_LE_FAST_SQRT
 #define IBTK_LE_FAST_SQRT 1
 #endif
@@ -191,12 +201,12 @@ __device__ __forceinline__ void stencil1d(double Xs, double Xraw, double xlo, do
     constexpr int FAM = KT<K>::FAM;
     if constexpr (FAM == 0) {
         // f.m4:1316 (X_o_dx), :1360-1365 (istart/istop)
-        // MUL: near a NINT tie the product can round to the other side of it than
-        // the quotient (which the bin key uses), moving the stencil one cell.
-        // At a tie the end weight of these kernels is 0 (r = 0 or 1), so the
-        // point that may then fall outside the key's bands carries a weight of
-        // an ulp's order: within the spread's tolerance.
-        const double X_o_dx = MUL ? (Xs - xlo) * inv_dx : (Xs - xlo) / dx;
+        // MUL: should the corrected product ever round to the other side of a NINT
+        // tie than the quotient (which the bin key uses), the stencil moves one
+        // cell; at a tie the end weight of these kernels is 0 (r = 0 or 1), so
+        // the point that may then fall outside the key's bands carries a weight
+        // of an ulp's order: within the spread's tolerance.
+        const double X_o_dx = MUL ? quotient_mul(Xs - xlo, dx, inv_dx) : (Xs - xlo) / dx;
         st.icl = closed_weights<K, MUL && IBTK_LE_FAST_SQRT>(X_o_dx, ilo, st.w, K6);
         const int icu = st.icl + (W - 1);
         st.ist = max(glo - st.icl, 0);

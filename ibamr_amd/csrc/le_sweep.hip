@@ -1843,7 +1843,7 @@ __device__ __forceinline__ void spread_setup(const Params& p, const CompDesc& cd
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
         const double Xraw = (FAM == 2) ? p.X[(int64_t)3 * cdat.s + d] : cdat.X[d];
-        // X/dx by a multiply (see stencil1d for ties)
+        // X/dx by a multiply and one correction (quotient_mul; see stencil1d for ties)
 #if IBTK_LE_DIAG_SPREAD & 2  // diagnostic: trivial weights (results wrong by design)
         {
             const double xo = (cdat.X[d] - cd.xlo[d]) * inv_d[d];
@@ -1856,12 +1856,12 @@ __device__ __forceinline__ void spread_setup(const Params& p, const CompDesc& cd
         }
 #else
         if constexpr (K == K_IB_4) {
-            // IB_4 (f.m4:1447-1457) with X/dx by a multiply and the anchor by rint: NINT
+            // IB_4 (f.m4:1447-1457) with X/dx by quotient_mul and the anchor by rint: NINT
             // differs from it only at a tie, where the stencil one cell over carries the
             // same weights on the same points (the end weight is 0 at r = 0 or 1).  The
             // weights keep 0.125 (a -+ q) unscaled here (t[]): the x / z scalings below
             // fold 0.125 into V / 1 / h^3 -- exact powers of two, the same bits.
-            const double xo = (cdat.X[d] - cd.xlo[d]) * inv_d[d];
+            const double xo = quotient_mul(cdat.X[d] - cd.xlo[d], p.bg.dx[d], inv_d[d]);
             const double n = __builtin_rint(xo);
             st[d].icl = (int)n + cd.ilower[d] - 2;
             const double r = xo - (n - 0.5);

@@ -446,7 +446,13 @@ class Level:
     geoms: the patches' Geometry (one dx); lists[q]: patch q's list, either None
     (every marker) or (indices int32 device tensor, Xshift float64 device tensor
     or None).  interp/spread take the arrays of every patch, patch by patch
-    (``arrays[q]`` = that patch's list of component arrays)."""
+    (``arrays[q]`` = that patch's list of component arrays).
+
+    The patches may differ in extent, lie at any (negative) index, leave gaps and come in any
+    order; side, cell, node and edge data all go through interp, spread, zero and zero_spread.
+    fill_ghosts and the fused fill_interp are narrower: side or cell data on equal patches that
+    tile their bounding box (tiles may be missing); unequal patches raise IBTKLEError (ARG,
+    "equal patches and ghost widths only") before anything is written."""
 
     def __init__(self, ctx: Context, geoms: Sequence[Geometry], kernel: str, X: torch.Tensor, lists):
         if len(geoms) != len(lists) or not geoms:
