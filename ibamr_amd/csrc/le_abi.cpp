@@ -163,10 +163,6 @@ struct ibtk_le_ctx_s {
     bool timing = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool ev_valid = false;
-    // the 3-D spread's F gather runs on a side stream, concurrent with the candidate-stream
-    // rebuild on `stream` (gather_fork / gather_join), created on first use
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // pinned host staging of small read-backs (d2h_sync): a copy into pageable memory is a
     // staged, blocking copy of its own
     void* hstage = nullptr;
@@ -236,7 +232,7 @@ struct ibtk_le_markers_s {
     // ibtk_le_markers_rebin: the last binning's list (n_dev of a fixed-capacity one) and its scratch
     const int* n_dev = nullptr;
     bool binned3 = false;                 // a 3-D column binning (ibtk_le_markers_bin(_count) / level_bin) holds
-    DevBuf rb_cin, rb_cout, rb_d, rb_dpre, rb_mstart, rb_ps2, rb_mbits, rb_wcnt, rb_wpre, rb_mlist, rb_scr, rb_big,
+    DevBuf rb_cin, rb_cout, rb_d, rb_mstart, rb_ps2, rb_mbits, rb_wcnt, rb_wpre, rb_mlist, rb_scr, rb_big,
         rb_nbig;
     int rb_zeroed_nb = -1;                // rb_cin / rb_cout are zero for this many buckets
     int items_sig[12] = {-1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // what the item table was built with (cuts, strip, target, heavy)
@@ -285,12 +281,6 @@ extern "C" int ibtk_le_ctx_destroy(ibtk_le_ctx ctx) {
         b->release();
     if (ctx->ev0) hipEventDestroy(ctx->ev0);
     if (ctx->ev1) hipEventDestroy(ctx->ev1);
-    if (ctx->side) {
-        hipStreamSynchronize(ctx->side);
-        hipStreamDestroy(ctx->side);
-    }
-    if (ctx->ev_fork) hipEventDestroy(ctx->ev_fork);
-    if (ctx->ev_join) hipEventDestroy(ctx->ev_join);
     if (ctx->hstage) hipHostFree(ctx->hstage);
     delete ctx;
     return IBTK_LE_OK;
@@ -343,8 +333,6 @@ extern "C" int ibtk_le_ctx_tune(ibtk_le_ctx ctx, const char* key, int value) {
     else if (k == "heavy_first") t.heavy_first = value;
     else if (k == "strip") t.strip = value;
     else if (k == "xcd_block") t.xcd_block = value;
-    else if (k == "interp3") t.interp3 = value;
-    else if (k == "side_gather") t.side_gather = value;
     else if (k == "f_stream") t.f_stream = value;
     else return fail(IBTK_LE_ERR_ARG, "unknown tuning key %s", key);
     return IBTK_LE_OK;
@@ -410,21 +398,17 @@ static void array_strides(const ibtk_le_patch_geom* g, const int64_t n[3], int64
     sd = s2 * n[2];
 }
 
-// Brick grid over key cells: every key whose stencil can touch any array of the
-// patch (ghost box, + 1 for the shifted-frame extra face/node) gets a brick.
+// 2-D brick grid over key cells: every key whose stencil can touch any array of
+// the patch (ghost box, + 1 for the shifted-frame extra face/node) gets a brick.
 static int make_bin_geom(const ibtk_le_patch_geom* g, int kernel, BinGeom& bg) {
     const KernelInfo ki = kKernelInfo[kernel];
-    const int B = g->ndim == 3 ? BRICK3 : BRICK2;
+    const int B = BRICK2;
     std::memset(&bg, 0, sizeof(bg));
-    bg.ndim = g->ndim;
-    bg.shift = g->ndim == 3 ? 9 : 8;
+    bg.ndim = 2;
+    bg.shift = 8;  // log2(B * B)
+    bg.nb[2] = bg.nt[2] = 1;
     long long nb = 1;
-    for (int d = 0; d < 3; ++d) {
-        if (d >= g->ndim) {
-            bg.nb[d] = 1;
-            bg.nt[d] = 1;
-            continue;
-        }
+    for (int d = 0; d < 2; ++d) {
         const int lo = g->ilower[d] - g->gcw[d];
         const int hi = g->iupper[d] + g->gcw[d] + 1;
         bg.kmin[d] = lo - ki.HI;
@@ -603,7 +587,7 @@ extern "C" int ibtk_le_markers_destroy(ibtk_le_markers m) {
     for (DevBuf* b : {&m->sorted_key, &m->sorted_l, &m->sorted_s, &m->sorted_X, &m->sorted_a, &m->plane_start, &m->indices,
                       &m->xshift, &m->cand_cnt, &m->cand_off, &m->cand_idx, &m->last, &m->qdst, &m->items,
                       &m->nsub, &m->isub, &m->nitems, &m->pd, &m->entry_off, &m->qin, &m->owner, &m->int_off,
-                      &m->rb_cin, &m->rb_cout, &m->rb_d, &m->rb_dpre, &m->rb_mstart, &m->rb_ps2, &m->rb_mbits,
+                      &m->rb_cin, &m->rb_cout, &m->rb_d, &m->rb_mstart, &m->rb_ps2, &m->rb_mbits,
                       &m->rb_wcnt, &m->rb_wpre, &m->rb_mlist, &m->rb_scr, &m->rb_big, &m->rb_nbig, &m->cs_cnt,
                       &m->cs_off, &m->cs_pos, &m->cs_src, &m->cs_off_z, &m->zbits, &m->zst, &m->sel_gs})
         b->release();
@@ -779,7 +763,7 @@ extern "C" int ibtk_le_markers_rebin(ibtk_le_ctx ctx, ibtk_le_markers m, const d
     int rc;
     const size_t bb = sizeof(int) * ((size_t)nb + 2), wb = sizeof(int) * ((size_t)nw + 1);
     const bool fresh = m->rb_zeroed_nb != nb || !m->rb_cin.p || m->rb_cin.cap < bb || m->rb_cout.cap < bb;
-    for (DevBuf* b : {&m->rb_cin, &m->rb_cout, &m->rb_d, &m->rb_dpre, &m->rb_mstart, &m->rb_ps2, &m->rb_big})
+    for (DevBuf* b : {&m->rb_cin, &m->rb_cout, &m->rb_d, &m->rb_mstart, &m->rb_ps2, &m->rb_big})
         if ((rc = b->ensure(bb))) return rc;
     for (DevBuf* b : {&m->rb_mbits, &m->rb_wcnt, &m->rb_wpre})
         if ((rc = b->ensure(wb))) return rc;
@@ -827,7 +811,6 @@ extern "C" int ibtk_le_markers_rebin(ibtk_le_ctx ctx, ibtk_le_markers m, const d
     r.cin = m->rb_cin.as<int>();
     r.cout = m->rb_cout.as<int>();
     r.d = m->rb_d.as<int>();
-    r.dpre = m->rb_dpre.as<int>();
     r.mstart = m->rb_mstart.as<int>();
     r.mlist = m->rb_mlist.as<int>();
     r.scratch = m->rb_scr.as<int>();
@@ -903,8 +886,7 @@ static int markers_bin_impl(ibtk_le_ctx ctx, ibtk_le_markers m, const ibtk_le_pa
     m->n_dev = n_dev;
     m->binned3 = cols;
     int rc = 0;
-    const int B = geom->ndim == 3 ? BRICK3 : BRICK2;
-    const int nplanes = cols ? cg.nbuckets : bg.nbricks * B;  // bucket starts: nplanes + 1
+    const int nplanes = cols ? cg.nbuckets : bg.nbricks * BRICK2;  // bucket starts: nplanes + 1
     if ((rc = m->plane_start.ensure(sizeof(int) * (size_t)(nplanes + 1)))) return rc;
     if (n == 0) {
         HIP_TRY(hipMemsetAsync(m->plane_start.p, 0, sizeof(int) * (size_t)(nplanes + 1), s));
@@ -937,7 +919,7 @@ static int markers_bin_impl(ibtk_le_ctx ctx, ibtk_le_markers m, const ibtk_le_pa
     p.Xshift = m->has_xshift ? m->xshift.as<double>() : nullptr;
     p.n_dev = n_dev;
     if (cols) HIP_TRY(launch_bin_col(kernel, p, n, ctx->keys_in.as<unsigned>(), ctx->vals_in.as<int>(), s));
-    else HIP_TRY(launch_bin(geom->ndim, kernel, p, n, ctx->keys_in.as<unsigned>(), ctx->vals_in.as<int>(), s));
+    else HIP_TRY(launch_bin(kernel, p, n, ctx->keys_in.as<unsigned>(), ctx->vals_in.as<int>(), s));
     int end_bit = 1;
     if (cols) {
         while ((1ULL << end_bit) <= (unsigned long long)cg.nbuckets) ++end_bit;
@@ -956,9 +938,9 @@ static int markers_bin_impl(ibtk_le_ctx ctx, ibtk_le_markers m, const ibtk_le_pa
         if ((rc = gather_buckets(ctx, m, kernel, p, n, nplanes))) return rc;
         if (int rc2 = build_items(ctx, m, kernel)) return rc2;
     } else {
-        HIP_TRY(launch_brick_start(m->sorted_key.as<unsigned>(), n, nplanes, bg.shift - (geom->ndim == 3 ? 3 : 4),
+        HIP_TRY(launch_brick_start(m->sorted_key.as<unsigned>(), n, nplanes, bg.shift - 4,  // 4 = log2(BRICK2)
                                    m->plane_start.as<int>(), s));
-        HIP_TRY(launch_gather_sorted(geom->ndim, p, n, m->sorted_s.as<int>(), m->sorted_X.as<double>(), s));
+        HIP_TRY(launch_gather_sorted(p, n, m->sorted_s.as<int>(), m->sorted_X.as<double>(), s));
     }
     return IBTK_LE_OK;
 }
@@ -1158,8 +1140,7 @@ int ibtk_le::interp_impl(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, int cen
         if (geom->ndim == 3)
             HIP_TRY(launch_interp_sweep(kernel, p, m->n, ctx->stream, t ? ctx->ev0 : nullptr, t ? ctx->ev1 : nullptr));
         else
-            HIP_TRY(launch_interp(geom->ndim, kernel, p, m->n, ctx->stream, t ? ctx->ev0 : nullptr,
-                                  t ? ctx->ev1 : nullptr));
+            HIP_TRY(launch_interp(kernel, p, m->n, ctx->stream, t ? ctx->ev0 : nullptr, t ? ctx->ev1 : nullptr));
         if (t) ctx->ev_valid = true;
     }
     return IBTK_LE_OK;
@@ -1192,65 +1173,36 @@ extern "C" int ibtk_le_fill_interp(ibtk_le_ctx ctx, ibtk_le_markers m, int kerne
     return ibtk_le::interp_impl(ctx, m, kernel, centering, axis, geom, q_dev, q_depth, Q_dev, Q_depth, X_dev, true, per);
 }
 
-// Super-brick candidate lists (k_cand): count, exclusive scan, write.  Built once
-// per binning, on the first spread after it.
+// Super-brick candidate lists of the 2-D spread (k_cand): count, exclusive scan,
+// write.  Built once per binning, on the first spread after it.  A super-brick is
+// 4 bricks, and a marker is a candidate of at most 4 super-bricks.
 static int build_candidates(ibtk_le_ctx ctx, ibtk_le_markers m, const Params& p) {
     if (m->cand_valid) return IBTK_LE_OK;
     const hipStream_t s = ctx->stream;
-    const int items = m->bg.nbricks / (m->ndim == 3 ? 8 : 4) * cand_classes(m->ndim, m->kernel);
+    const int items = m->bg.nbricks / 4 * cand_classes(m->kernel);
     int rc = 0;
     if ((rc = m->cand_cnt.ensure(sizeof(int) * (size_t)(items + 1)))) return rc;
     if ((rc = m->cand_off.ensure(sizeof(int) * (size_t)(items + 1)))) return rc;
-    if ((rc = m->cand_idx.ensure(sizeof(int) * (size_t)m->n * (m->ndim == 3 ? 8 : 4)))) return rc;
+    if ((rc = m->cand_idx.ensure(sizeof(int) * (size_t)m->n * 4))) return rc;
     HIP_TRY(hipMemsetAsync(m->cand_cnt.p, 0, sizeof(int) * (size_t)(items + 1), s));
-    HIP_TRY(launch_cand(m->ndim, m->kernel, p, false, m->cand_cnt.as<int>(), nullptr, s));
+    HIP_TRY(launch_cand(m->kernel, p, false, m->cand_cnt.as<int>(), nullptr, s));
     size_t tb = 0;
     HIP_TRY(launch_scan(nullptr, tb, m->cand_cnt.as<int>(), m->cand_off.as<int>(), items + 1, s));
     if ((rc = ctx->temp.ensure(tb))) return rc;
     tb = ctx->temp.cap;
     HIP_TRY(launch_scan(ctx->temp.p, tb, m->cand_cnt.as<int>(), m->cand_off.as<int>(), items + 1, s));
-    HIP_TRY(launch_cand(m->ndim, m->kernel, p, true, m->cand_off.as<int>(), m->cand_idx.as<int>(), s));
+    HIP_TRY(launch_cand(m->kernel, p, true, m->cand_off.as<int>(), m->cand_idx.as<int>(), s));
     m->cand_valid = true;
     return IBTK_LE_OK;
 }
 
-// The 3-D spread's F gather (sorted_F from Q and sorted_s, both ready on `stream`) does not
-// depend on the candidate stream, whose rebuild after a re-binning (k_cand_count, the scan,
-// k_cand_write: about 1 ms at cfg4) leaves CUs idle: when the stream is rebuilt, the
-// gather runs beside it on the side stream (cfg4 moving: spread 14.6 -> 14.4 ms a step,
-// profiles/r06/side_gather_ab.txt); a standing stream keeps the gather in line.  The fork orders the gather after everything on `stream` so far (the
-// binning, the previous sweep still reading sorted_F); the join orders the sweep after it.
-// Worth its cross-stream hops (about 0.05 ms a step) only on a large gather: cfg4 (1e8
-// markers) gains 0.2 ms, cfg5 (1e7, a level) loses 0.04 ms; the gain scales with n, even
-// at about 2.5e7.  side_gather: 0 auto (n >= 2^25), 1 always, -1 never.
-// The gather pass itself is the alternative (f_stream -1) to the 3-D sweep reading F at its
-// marker row through the candidate stream's source rows (f_stream 1, Params::cs_src): no
-// sorted_F, no pass, no side stream.  f_stream 0, the default, is 1 (cfg4: the 1.2-ms pass
-// goes, the sweep gives 0.4 ms back).
+// The 3-D sweep reads F at its marker row through the candidate stream's source rows
+// (f_stream 1, Params::cs_src): no sorted_F and no pass before the sweep.  f_stream 0, the
+// default, is 1 (cfg4: the 1.2-ms pass goes, the sweep gives 0.4 ms back; DESIGN.md section
+// 7).  f_stream -1 gathers F into sorted order in line before the sweep (launch_gather_F):
+// the bit-for-bit reference of the default.
 static bool f_stream(ibtk_le_ctx ctx, ibtk_le_markers) {
     return ctx->tune.f_stream >= 0;
-}
-static bool side_gather(ibtk_le_ctx ctx, ibtk_le_markers m) {
-    const int t = ctx->tune.side_gather;
-    return !f_stream(ctx, m) && (t > 0 || (t == 0 && m->n >= (1 << 25)));
-}
-static int gather_fork(ibtk_le_ctx ctx, const Params& p) {
-    if (!ctx->side) {  // created together, or not at all
-        if (!ctx->ev_fork) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-        if (!ctx->ev_join) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-        hipStream_t st = nullptr;
-        HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        ctx->side = st;
-    }
-    HIP_TRY(hipEventRecord(ctx->ev_fork, ctx->stream));
-    HIP_TRY(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
-    HIP_TRY(launch_gather_F(p, ctx->side));
-    HIP_TRY(hipEventRecord(ctx->ev_join, ctx->side));
-    return IBTK_LE_OK;
-}
-static int gather_join(ibtk_le_ctx ctx) {
-    HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-    return IBTK_LE_OK;
 }
 
 static int spread_impl(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, int centering, int axis,
@@ -1579,26 +1531,18 @@ static int spread_impl(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, int cente
     for (int first = 0; first < nc; first += MAXC) {
         const int cnt = std::min(MAXC, nc - first);
         if (int rc = make_comps(geom, centering, axis, q_dev, q_depth, Q_depth, first, cnt, p)) return rc;
-        const bool side = geom->ndim == 3 && side_gather(ctx, m) && !cand_stream_built(m, false);
-        if (side)
-            if (int rc = gather_fork(ctx, p)) return rc;
-        if (geom->ndim == 3)
-            if (int rc = cand_stream(ctx, m, p)) return rc;
-        if (side)
-            if (int rc = gather_join(ctx)) return rc;
         const bool t = ctx->timing && first == 0;
-        const size_t nst = (size_t)m->item_bound * cnt * 8;
-        if (geom->ndim == 3)
-            if (int rc = stamps_begin(ctx, nst, p)) return rc;
         if (geom->ndim == 3) {
+            if (int rc = cand_stream(ctx, m, p)) return rc;
+            const size_t nst = (size_t)m->item_bound * cnt * 8;
+            if (int rc = stamps_begin(ctx, nst, p)) return rc;
             if (int rc = adds_begin(ctx, p, first == 0)) return rc;
-            HIP_TRY(launch_spread_sweep(kernel, p, ctx->stream, t ? ctx->ev0 : nullptr, t ? ctx->ev1 : nullptr,
-                                        !side));
+            HIP_TRY(launch_spread_sweep(kernel, p, ctx->stream, t ? ctx->ev0 : nullptr, t ? ctx->ev1 : nullptr));
             if (int rc = adds_end(ctx, p)) return rc;
+            if (int rc = stamps_report(ctx, nst, p)) return rc;
         } else {
-            HIP_TRY(launch_spread(geom->ndim, kernel, p, ctx->stream, t ? ctx->ev0 : nullptr, t ? ctx->ev1 : nullptr));
+            HIP_TRY(launch_spread(kernel, p, ctx->stream, t ? ctx->ev0 : nullptr, t ? ctx->ev1 : nullptr));
         }
-        if (int rc = stamps_report(ctx, nst, p)) return rc;
         if (t) ctx->ev_valid = true;
     }
     return IBTK_LE_OK;
@@ -1938,18 +1882,13 @@ static int level_spread_impl(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, int
         if (int rc = ctx->fbuf.ensure(sizeof(double) * (size_t)m->n * (size_t)nc)) return rc;
         p.sorted_F = ctx->fbuf.as<double>();
     }
-    const bool side = side_gather(ctx, m) && !cand_stream_built(m, false);
-    if (side)
-        if (int rc = gather_fork(ctx, p)) return rc;
     if (int rc = cand_stream(ctx, m, p)) return rc;
-    if (side)
-        if (int rc = gather_join(ctx)) return rc;
     const bool t = ctx->timing;
     ctx->ev_valid = false;
     const size_t nst = (size_t)m->item_bound * nc * 8;
     if (int rc = stamps_begin(ctx, nst, p)) return rc;
     if (int rc = adds_begin(ctx, p, true)) return rc;
-    HIP_TRY(launch_spread_sweep(kernel, p, ctx->stream, t ? ctx->ev0 : nullptr, t ? ctx->ev1 : nullptr, !side));
+    HIP_TRY(launch_spread_sweep(kernel, p, ctx->stream, t ? ctx->ev0 : nullptr, t ? ctx->ev1 : nullptr));
     if (int rc = adds_end(ctx, p)) return rc;
     if (int rc = stamps_report(ctx, nst, p)) return rc;
     if (t) ctx->ev_valid = true;

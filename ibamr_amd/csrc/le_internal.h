@@ -40,8 +40,7 @@ constexpr KernelInfo kKernelInfo[K_COUNT] = {
 };
 
 constexpr int MAXC = 4;        // components processed by one launch
-constexpr int BRICK3 = 8;      // brick edge (cells) in 3-D: 8^3 = 512 cells
-constexpr int BRICK2 = 16;     // brick edge in 2-D: 16^2 = 256 cells
+constexpr int BRICK2 = 16;     // brick edge (cells) of the 2-D path: 16^2 = 256 cells
 constexpr int BLOCK = 256;     // threads per workgroup (4 waves)
 constexpr int TILE = 4;        // bricks per tile edge
 
@@ -62,10 +61,11 @@ struct CompDesc {
     int64_t s1, s2;  // strides of dims 1 and 2 (elements)
 };
 
-// The brick grid over stencil-anchor ("key") cells.  Bricks (8^3 cells in 3-D,
-// 16^2 in 2-D) are numbered tile by tile (tiles of 4^NDIM bricks, tiles in
-// linear order), Morton order inside a tile; an aligned 2^NDIM group of bricks
-// (a spread "super-brick") therefore has 2^NDIM consecutive ids.
+// The brick grid over stencil-anchor ("key") cells of the 2-D path.  Bricks of
+// 16^2 cells are numbered tile by tile (tiles of 4x4 bricks, tiles in linear
+// order), Morton order inside a tile; an aligned 2x2 group of bricks (a spread
+// "super-brick") therefore has 4 consecutive ids.  (The 3-D path bins by
+// columns, ColGeom below; of this struct it sets ndim, xlo, dx and ilower alone.)
 struct BinGeom {
     int ndim;
     int kmin[3];       // key cell of brick (0,0,0), cell (0,0,0)
@@ -114,12 +114,7 @@ struct SweepTune {
     int heavy_target = 0;  // a heavy item's pieces: own markers per piece (0: the default, le_sweep.hip HEAVY_TARGET)
     int heavy_min_piece = 0;  // ... and planes per piece, at least (0: HEAVY_MIN_PIECE)
     int heavy_first = 0;   // heavy items head the table (0, the default) or keep their place (-1)
-    int interp3 = 0;       // 3-D interp of three components on one patch: 1 = one workgroup per item for
-                           // all three (k_interp3: fewer bytes, measured slower); 0 = a workgroup per component
-    int side_gather = 0;   // 3-D spread: the F gather on the side stream beside the candidate-stream
-                           // rebuild (1), in line before the sweep (-1), or 0 (the default): on
-                           // the side stream from 2^25 markers
-    int f_stream = 0;      // 3-D spread: F read at its marker row through the candidate stream's source
+    int f_stream = 0;     // 3-D spread: F read at its marker row through the candidate stream's source
                            // rows (1), gathered into sorted order by a pass before the sweep (-1), or 0:
                            // the default, which is 1
 };
@@ -218,15 +213,15 @@ struct Params {
     int lvl_n[3] = {0, 0, 0};  // cells per patch and dim
 };
 
-// Host-side launchers (le_kernels.hip).
-hipError_t launch_bin(int ndim, int kernel, const Params& p, int n, unsigned* keys, int* vals, hipStream_t s);
+// Host-side launchers.  The 2-D brick path (le_hot.hip):
+hipError_t launch_bin(int kernel, const Params& p, int n, unsigned* keys, int* vals, hipStream_t s);
 hipError_t launch_brick_start(const unsigned* keys, int n, int nbricks, int shift, int* bs, hipStream_t s);
-hipError_t launch_gather_sorted(int ndim, const Params& p, int n, int* sorted_s, double* sorted_X, hipStream_t s);
-hipError_t launch_interp(int ndim, int kernel, const Params& p, int n, hipStream_t s, hipEvent_t ev0,
-                         hipEvent_t ev1);
-hipError_t launch_spread(int ndim, int kernel, const Params& p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
-hipError_t launch_cand(int ndim, int kernel, const Params& p, bool write, int* counts_or_offs, int* out, hipStream_t s);
-int cand_classes(int ndim, int kernel);  // candidate classes per super-brick
+hipError_t launch_gather_sorted(const Params& p, int n, int* sorted_s, double* sorted_X, hipStream_t s);
+hipError_t launch_interp(int kernel, const Params& p, int n, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+hipError_t launch_spread(int kernel, const Params& p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+hipError_t launch_cand(int kernel, const Params& p, bool write, int* counts_or_offs, int* out, hipStream_t s);
+int cand_classes(int kernel);  // candidate classes per super-brick
+// Shared helpers (le_aux.hip, le_sort.hip)
 hipError_t launch_mark(int ndim, int kernel, const Params& p, int n, unsigned char** masks, hipStream_t s);
 hipError_t launch_sort(void* temp, size_t& temp_bytes, const unsigned* kin, unsigned* kout, const int* vin,
                        int* vout, int n, int end_bit, hipStream_t s);
@@ -250,7 +245,6 @@ struct RebinBufs {
     int* cin;              // movers into bucket b (0 on entry; consumed back to 0)
     int* cout;             // movers out of bucket b (0 on entry; reset)
     int* d;                // scratch: per block of buckets, the sums of (cin - cout, cin) as int2
-    int* dpre;             // (unused)
     int* mstart;           // exclusive prefix of cin: bucket b's movers are mlist[mstart[b] .. mstart[b+1])
     int* mlist;            // the movers' l, per bucket sorted by l
     int* scratch;          // long lists' sort
@@ -401,10 +395,8 @@ hipError_t launch_fp_gather(int cls, int ndim, const unsigned* skeys, const int*
 hipError_t launch_gather_col(int kernel, const Params& p, int n, int* sorted_s, double* sorted_X,
                              const unsigned* sorted_key, int nbuckets, int* bucket_start, hipStream_t s);
 hipError_t launch_interp_sweep(int kernel, const Params& p, int n, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
-// gather = false: the spread values (sorted_F) were gathered already (launch_gather_F, on
-// the context's side stream while the candidate stream was rebuilt)
-hipError_t launch_spread_sweep(int kernel, const Params& p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1,
-                               bool gather = true);
+// without p.cs_src the sweep first gathers the spread values into sorted_F (launch_gather_F)
+hipError_t launch_spread_sweep(int kernel, const Params& p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 hipError_t launch_gather_F(const Params& p, hipStream_t s);
 void sweep_segments(const ColGeom& cg, int& S, int& nseg, int seg_items, bool level);
 hipError_t launch_item_table(int kernel, const Params& p, int target, int heavy, int* nsub, int* start, SweepItem* tab, int* ntot,

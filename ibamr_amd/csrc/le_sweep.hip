@@ -1213,234 +1213,6 @@ __global__ __launch_bounds__(SW * IWAVES) void k_interp_sweep(Params p) {
     }
 }
 
-// The three components of an interp item in one workgroup (k_interp3): WPC waves per
-// component stage its ring (wave w: component w / WPC; the group's new planes jw, jw + WPC,
-// ... of it, jw = w mod WPC), so the workgroup holds three rings (3 x 47 KB for IB_4: one
-// workgroup per CU).  The markers are the workgroup's, not a component's: lane L of the
-// group takes component L mod 3 of pool marker L / 3 (64 WPC markers a round), so a
-// marker's position and index are read once for its three sums -- not once per component
-// item -- and the three lanes of a marker store its three Q values next to each other: the
-// Q record is written whole, not 8 bytes at a time by three items at three different times.
-// Each sum is interp_marker's, in the Fortran order: bitwise the per-component kernel's (and
-// the oracle's).  PF groups of planes are in flight per wave in registers (a group's planes
-// are loaded PF groups before they are put).  Closed-form kernels, one patch, three
-// components.
-constexpr int I3C = 3;  // components of a k_interp3 item
-// The rings lie RSTR = NSL PVP + I3PAD doubles apart: the three lanes of a marker read the
-// same stencil offsets in the three rings, and with rings a multiple of 32 doubles apart
-// those reads hit one bank pair (ds_read_b64: a double's banks are its index mod 32) --
-// a 3-way conflict on every read (SQ: LDS waits 2.3x the per-component kernel's).  11 and
-// 22 doubles apart mod 32 they do not.
-constexpr int I3PAD = 11;
-// Measured on cfg4 (round 6, profiles/r06): 4 waves a component and one group of planes in
-// flight (12 waves, 146 VGPRs) is the fastest form -- 2 waves a component with one or two
-// groups in flight 11.7-12.1 ms, 1 wave with two 15.4 ms, components dealt by wave instead
-// of by lane 10.4-10.6 ms, against 10.1-10.3 ms -- and still 3-6 % slower than the
-// per-component kernel (9.7 ms) although it moves 20 % fewer bytes (44.6 against 55.4 GB
-// per launch): one 141-KB workgroup per CU waits at each group's barrier for the slowest
-// of its 12 plane loads with nothing else to run, where three independent 4-wave
-// workgroups cover each other's waits.  So k_interp_sweep stays the default and this one
-// runs on request (ctx_tune interp3 = 1).
-constexpr int I3WPC = 4, I3PF = 1;
-template <int K> struct I3Sh {
-    using S = ISh<K>;
-    static constexpr int RSTR = S::NSL * S::PVP + I3PAD;
-    static constexpr size_t lds = sizeof(double) * I3C * RSTR;
-    static constexpr bool fits = S::FAM == 0 && lds <= 160 * 1024;
-};
-template <int K, int WPC, int PF>
-__global__ __launch_bounds__(SW * I3C * WPC) void k_interp3(Params p) {
-    using S = ISh<K>;
-    static_assert(I3Sh<K>::fits, "k_interp3: closed-form kernels whose three rings fit the LDS");
-    static_assert(IWAVES % WPC == 0, "a component's new planes of a group split evenly over its waves");
-    constexpr int LO = S::LO, HI = S::HI, RX = S::RX, NPT = S::NPT, PVP = S::PVP;
-    constexpr int PPW = IWAVES / WPC;    // planes a wave stages per group
-    constexpr int I3M = WPC * SW;        // pool markers a round
-    constexpr int RSTR = I3Sh<K>::RSTR;  // ring stride (doubles)
-    __shared__ double ring[I3C * RSTR];
-    const int it = sweep_item(p, 1);
-    if (it < 0) return;
-    const SweepItem si = p.items[it];
-    const int col = si.col;
-    const int a0 = si.p0, a1 = si.p1;  // the item's anchor planes
-    const int lane = lane_id();
-    const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    const int cw = w / WPC, jw = w - cw * WPC;  // the wave's staging: component cw, planes jw + WPC t of a group
-    const ColGeom& cg = p.cg;
-    const int* const bs = p.plane_start;
-    gdouble* const sorted_X = cur_sorted_X(p);
-    if (p.zmode) {  // the planes the item reads: a0 + LO .. a1 - 1 + HI
-        const bool inner = cg.org[2] + a0 + LO >= p.zlo && cg.org[2] + a1 - 1 + HI <= p.zhi;
-        if (inner != (p.zmode == 1)) return;
-    }
-    {
-        bool any = false;  // the same answer in every wave
-        for (int a = a0 + lane; a < a1; a += SW) any = any || bs[bucket(cg, a, col, NBAND)] > bs[bucket(cg, a, col, 0)];
-        if (!__any(any)) return;
-    }
-    const int cx = col % cg.ncx, cy = col / cg.ncx;
-    const int gx0 = cg.org[0] + cx * COLX + LO, gy0 = cg.org[1] + cy * COLY + LO;
-    const int zorg = cg.org[2];
-    const int nlast = p.nsorted - 1;
-    // ---- staging: the wave's component cw (wave-uniform), as k_interp_sweep stages one
-    const CompDesc cd = cw == 0 ? p.comp[0] : (cw == 1 ? p.comp[1] : p.comp[2]);
-    auto image = [&](int i, int d) {
-        if (!p.iper[d] || (i >= cd.ilower[d] && i <= cd.iupper[d])) return i;
-        const int n = cd.iupper[d] - cd.ilower[d] + 1;
-        int r = (i - cd.ilower[d]) % n;
-        return cd.ilower[d] + (r < 0 ? r + n : r);
-    };
-    const bool xlast = cd.xcell, ylast = cd.ycell;  // (FAM 0: the unread last staged column / row)
-    unsigned poff[NPT];
-#pragma unroll
-    for (int k = 0; k < NPT; ++k) {
-        const int q = min(lane + SW * k, S::PV - 1);
-        const int qx = q % RX, qy = q / RX;
-        const int gx = gx0 + qx, gy = gy0 + qy;
-        const bool in = gx >= cd.lo[0] && gx <= cd.hi[0] && gy >= cd.lo[1] && gy <= cd.hi[1] &&
-                        !(xlast && qx == RX - 1) && !(ylast && qy == S::RY - 1);
-        poff[k] = in ? 8u * (unsigned)((image(gx, 0) - cd.lo[0]) + (image(gy, 1) - cd.lo[1]) * (int)cd.s1) : OFF_NONE;
-    }
-    const int plast = a1 - 1 + HI;  // last plane the item reads
-    const unsigned plane_bytes = (unsigned)(8 * cd.s2);
-    auto plane_load = [&](int zr, double* v) __attribute__((always_inline)) {
-        const int z0 = zorg + min(zr, plast);
-        const bool zin = z0 >= cd.lo[2] && z0 <= cd.hi[2];
-        const int z = zin ? image(z0, 2) : z0;
-        const int zc = min(max(z, cd.lo[2]), cd.hi[2]);
-        const auto pb = plane_rsrc(cd.u + (int64_t)(zc - cd.lo[2]) * cd.s2, zin ? plane_bytes : 0u);
-#pragma unroll
-        for (int k = 0; k < NPT; ++k) v[k] = buf_ld(pb, poff[k]);
-    };
-    double* const ring_w = ring + cw * RSTR;  // the staged component's ring
-    auto plane_put = [&](int zr, const double* v) {
-        double* sl = ring_w + islot<K>(zr) * PVP;
-#pragma unroll
-        for (int k = 0; k < NPT; ++k)
-            if (S::PV % SW == 0 || k < NPT - 1 || lane + SW * k < S::PV) sl[lane + SW * k] = v[k];
-    };
-    // ---- the lane's component cl (fixed: 3 I3M lanes a round) and its marker slot
-    const int cl = (int)threadIdx.x % I3C, ml = (int)threadIdx.x / I3C;
-    CompDesc cdl;
-#define I3SEL(f) cdl.f = cl == 0 ? p.comp[0].f : (cl == 1 ? p.comp[1].f : p.comp[2].f)
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        I3SEL(xlo[d]);
-        I3SEL(ilower[d]);
-        I3SEL(lo[d]);
-        I3SEL(hi[d]);
-    }
-    I3SEL(axis);
-    I3SEL(xcell);
-    I3SEL(ycell);
-    I3SEL(qcomp);
-#undef I3SEL
-    const double* const ring_l = ring + cl * RSTR;
-    struct Mk {
-        int q;  // the marker whose Q this entry writes (-1: a later duplicate entry does)
-        double X[3];
-    };
-    auto lds_barrier = [&]() {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    };
-    struct GSpan {
-        int beg[IWAVES];
-        int pre[IWAVES + 1];
-    };
-    auto gspan_load = [&](int a) {
-        const int k = lane < IWAVES ? lane : min(lane - IWAVES, IWAVES - 1);
-        const int ac = min(a + k, cg.nz - 1);
-        return bs[bucket(cg, ac, col, lane >= IWAVES && lane < 2 * IWAVES ? NBAND : 0)];
-    };
-    auto gspan_get = [&](int a, int v, GSpan& gsp) {
-        int acc = 0;
-#pragma unroll
-        for (int k = 0; k < IWAVES; ++k) {
-            const int b = __builtin_amdgcn_readlane(v, k);
-            const int e = a + k < a1 ? __builtin_amdgcn_readlane(v, IWAVES + k) : b;
-            gsp.beg[k] = b;
-            gsp.pre[k] = acc;
-            acc += e - b;
-        }
-        gsp.pre[IWAVES] = acc;
-    };
-    // round r of a group: pool marker I3M r + ml (clamped), with its anchor plane
-    auto mk_load = [&](const GSpan& gsp, int a, int r, Mk& m, int& am) {
-        const int tot = gsp.pre[IWAVES];
-        const int j = min(I3M * r + ml, max(tot - 1, 0));
-        int e = gsp.beg[0] + j, k = 0;
-#pragma unroll
-        for (int q = 1; q < IWAVES; ++q)
-            if (j >= gsp.pre[q]) {
-                e = gsp.beg[q] + (j - gsp.pre[q]);
-                k = q;
-            }
-        am = a + k;
-        e = min(e, nlast);
-        m.q = (p.qdst ? p.qdst : p.sorted_s)[e];
-        const D3 xs = ld3(sorted_X + (int64_t)3 * e);
-        m.X[0] = xs.v[0];
-        m.X[1] = xs.v[1];
-        m.X[2] = xs.v[2];
-    };
-    auto process = [&](int n, const Mk& m, int am) {  // round of n <= I3M markers
-        const bool act = ml < n;
-        double acc = 0.0;
-        if (act) acc = interp_marker<K>(p, cdl, ring_l, gx0, gy0, zorg, am, m.X, 0);
-        double* dst = (act && m.q >= 0) ? p.Qout + ((int64_t)p.Q_depth * m.q + cdl.qcomp) : p.sink + lane;
-        *dst = acc;
-    };
-    {  // prologue: planes a0 + LO .. a0 + HI - 1 into the rings
-        double pv[NPT];
-        for (int z = a0 + LO + jw; z < a0 + HI; z += WPC) {
-            plane_load(z, pv);
-            plane_put(z, pv);
-        }
-    }
-    // pv[b][t]: the group's new plane jw + WPC t, in register buffer b (b = group index mod PF)
-    double pv[PF][PPW][NPT];
-#pragma unroll
-    for (int b = 0; b < PF; ++b)
-#pragma unroll
-        for (int t = 0; t < PPW; ++t) plane_load(a0 + b * IWAVES + jw + WPC * t + HI, pv[b][t]);
-    GSpan gs;
-    gspan_get(a0, gspan_load(a0), gs);
-    Mk nxt;
-    int anx;
-    mk_load(gs, a0, 0, nxt, anx);
-    int vsp1 = gspan_load(a0 + IWAVES);
-    auto group = [&](int a, double (*pvb)[NPT]) __attribute__((always_inline)) {
-        lds_barrier();  // the previous group's reads are done
-#pragma unroll
-        for (int t = 0; t < PPW; ++t) plane_put(a + jw + WPC * t + HI, pvb[t]);
-        lds_barrier();  // planes a+LO .. a+IWAVES-1+HI of every component are in the rings
-        const Mk cur = nxt;
-        const int acur = anx;
-        const GSpan gc = gs;
-        gspan_get(a + IWAVES, vsp1, gs);
-        mk_load(gs, a + IWAVES, 0, nxt, anx);
-        vsp1 = gspan_load(a + 2 * IWAVES);
-#pragma unroll
-        for (int t = 0; t < PPW; ++t) plane_load(a + PF * IWAVES + jw + WPC * t + HI, pvb[t]);
-        const int tot = gc.pre[IWAVES];
-        Mk m = cur;
-        int am = acur;
-        for (int r = 0; I3M * r < tot; ++r) {  // (dense groups: the next round loads while this one sums)
-            const Mk now = m;
-            const int anow = am;
-            if (I3M * (r + 1) < tot) mk_load(gc, a, r + 1, m, am);
-            process(min(tot - I3M * r, I3M), now, anow);
-        }
-    };
-    for (int a = a0; a < a1; a += PF * IWAVES) {
-#pragma unroll
-        for (int b = 0; b < PF; ++b)
-            if (b == 0 || a + b * IWAVES < a1) group(a + b * IWAVES, pv[b]);
-    }
-}
-
 // Entries binned "outside" (no stencil point can reach any array): V = 0.
 __global__ __launch_bounds__(BLOCK) void k_interp_outside_col(Params p, int n) {
     const int first = p.plane_start[p.nbuckets_total];
@@ -2692,16 +2464,7 @@ template <int K>
 hipError_t launch_interp_sweep_t(const Params& p, int n, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
     if (ev0) (void)hipEventRecord(ev0, s);
     const long items = (long)p.item_bound * p.ncomp;
-    bool done = false;
-    if constexpr (I3Sh<K>::fits) {
-        // the three components of an item in one workgroup (k_interp3), on request
-        if (items > 0 && !p.pd && p.ncomp == I3C && p.tune.interp3 > 0) {
-            hipLaunchKernelGGL((k_interp3<K, I3WPC, I3PF>), dim3(sweep_grid(p, p.item_bound)), dim3(SW * I3C * I3WPC), 0,
-                               s, p);
-            done = true;
-        }
-    }
-    if (items > 0 && !done) {
+    if (items > 0) {
         const dim3 g(sweep_grid(p, items)), b(SW * IWAVES);
         if (p.pd && p.lvl_nbr) hipLaunchKernelGGL((k_interp_sweep<K, true, true>), g, b, 0, s, p);
         else if (p.pd) hipLaunchKernelGGL((k_interp_sweep<K, true>), g, b, 0, s, p);
@@ -2746,8 +2509,8 @@ hipError_t launch_gather_F(const Params& p, hipStream_t s) {
     return hipGetLastError();
 }
 template <int K>
-hipError_t launch_spread_sweep_t(const Params& p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, bool gather) {
-    if (gather && !p.cs_src)  // (cs_src: the sweep reads F at its row, no sorted_F)
+hipError_t launch_spread_sweep_t(const Params& p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+    if (!p.cs_src)  // (cs_src: the sweep reads F at its row, no sorted_F)
         if (hipError_t e = launch_gather_F(p, s); e != hipSuccess) return e;
     if (ev0) (void)hipEventRecord(ev0, s);  // the events bracket the sweep kernels alone
     // One launch of every component.  Closed-form kernels run them all on the 5-slot
@@ -2803,7 +2566,7 @@ hipError_t launch_item_table(int kernel, const Params& p, int target, int heavy,
 using BinColFn = hipError_t (*)(const Params&, int, unsigned*, int*, hipStream_t);
 using GatherColFn = hipError_t (*)(const Params&, int, int*, double*, const unsigned*, int, int*, hipStream_t);
 using InterpSwFn = hipError_t (*)(const Params&, int, hipStream_t, hipEvent_t, hipEvent_t);
-using SpreadSwFn = hipError_t (*)(const Params&, hipStream_t, hipEvent_t, hipEvent_t, bool);
+using SpreadSwFn = hipError_t (*)(const Params&, hipStream_t, hipEvent_t, hipEvent_t);
 static BinColFn pick_bin_col(int k) { IBTK_LE_DISPATCH_K(k, launch_bin_col_t) }
 static GatherColFn pick_gather_col(int k) { IBTK_LE_DISPATCH_K(k, launch_gather_col_t) }
 static InterpSwFn pick_interp_sweep(int k) { IBTK_LE_DISPATCH_K(k, launch_interp_sweep_t) }
@@ -2883,10 +2646,9 @@ hipError_t launch_interp_sweep(int kernel, const Params& p, int n, hipStream_t s
     InterpSwFn f = pick_interp_sweep(kernel);
     return f ? f(p, n, s, ev0, ev1) : hipErrorInvalidValue;
 }
-hipError_t launch_spread_sweep(int kernel, const Params& p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1,
-                               bool gather) {
+hipError_t launch_spread_sweep(int kernel, const Params& p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
     SpreadSwFn f = pick_spread_sweep(kernel);
-    return f ? f(p, s, ev0, ev1, gather) : hipErrorInvalidValue;
+    return f ? f(p, s, ev0, ev1) : hipErrorInvalidValue;
 }
 
 }  // namespace ibtk_le

@@ -1134,16 +1134,11 @@ int ibtk_le_ctx_enable_timing(ibtk_le_ctx ctx, int enable);
  * "heavy_min_piece" (the same for heavy items; defaults 2048 and 1), "strip" (column rows per
  * strip of the item order), "xcd_block" (light items over the XCDs in blocks of
  * this many table entries: 1 round-robin, -1 one range per XCD; default 8), and,
- * taking effect at the next interp, "interp3" (1: the three components of a one-patch
- * closed-form interp item in one workgroup -- each marker read once, each Q record written
- * whole; bitwise the same result; 0, the default: a workgroup per component), and,
- * taking effect at the next spread, "side_gather" (1: the 3-D spread's F gather on the
- * context's side stream, beside a candidate-stream rebuild; -1: in line before the sweep;
- * 0, the default: the side stream from 2^25 markers; bitwise the same result; it acts only
- * where the gather pass runs), and "f_stream" (1: the 3-D spread reads F at its marker row
+ * taking effect at the next spread, "f_stream" (1: the 3-D spread reads F at its marker row
  * through the candidate stream, which then carries each entry's row beside its sorted
  * position -- no gather pass and no sorted copy of F; -1: the gather pass into sorted
- * order before the sweep; 0: the default, which is 1; bitwise the same result).
+ * order, in line before the sweep; 0: the default, which is 1; bitwise the same result).
+ * Any other key returns IBTK_LE_ERR_ARG.
  * Interp results do not depend on them; spread results are bit-stable for fixed
  * settings and may differ in the last bits between settings (same-point adds
  * within one 64-candidate chunk follow its step and lane order, and the chunk

@@ -4,8 +4,8 @@ Every interp and spread entry point takes cell- and node-centred data of any dep
 library cuts the components into launches of MAXC = 4 (le_abi.cpp: interp_impl,
 spread_impl, zero_comps), offsets each component's array by ``depth_index * sd`` and
 its Q column by ``qcomp`` (make_comps), and the kernels loop or decode over ``ncomp``.
-The rest of the suite stops at depth 2; here depths 3 (REC3 gather, k_interp3), 4 (one
-full launch), 5 (a second launch with first > 0) and 9 (three launches) run through the
+The rest of the suite stops at depth 2; here depths 3 (REC3 gather), 4 (one full launch),
+5 (a second launch with first > 0) and 9 (three launches) run through the
 single-patch calls, the fused forms, the density-weighted spread, the level calls, the
 Fortran shims, the USER_DEFINED path, the ghost operations and mark_stencils.
 
@@ -485,36 +485,21 @@ def test_spread_ds_depth(le, ctx, oracle, kernel, ndim, depth):
 
 
 # --------------------------------------------------------------------------
-# f. interp3 tuning
+# f. a second launch of three components
 # --------------------------------------------------------------------------
-@pytest.mark.parametrize("centering,depth", [("cell", 3), ("node", 3), ("edge", 1), ("cell", 7)])
 @pytest.mark.parametrize("kernel", ["IB_4", "BSPLINE_4"])
-def test_interp3_depth_bitwise(le, kernel, centering, depth):
-    """test_interp3_bitwise's method on the centrings it leaves out: any three components are
-    eligible for k_interp3, and of cell depth 7 the second launch (Q columns 4, 5, 6 of 7)
-    alone."""
-    g = le._lib.load().ibtk_le_min_ghost_width(le.kernel_id(kernel))
-    geom = le.Geometry.periodic_unit([96, 64, 72], g)
-    rng = np.random.default_rng(17)
-    M = 20000
-    Xd = torch.from_numpy(rng.uniform(0.0, 1.0, (M, 3))).to(DEV)
-    u = Eul(geom, centering, depth, rng)
-    Qd = 3 if centering == "edge" else depth
-    out = []
-    for tune in (False, True):
-        cx = le.Context(0)
-        if tune:
-            cx.tune("interp3", 1)
-        m = le.Markers(cx).bin(geom, kernel, Xd)
-        Q = Lag(M, Qd)
-        le.interp(cx, m, kernel, centering, geom, u.q, Q.v, Xd, q_depth=depth)
-        cx.synchronize()
-        Q.check()
-        assert not bool(torch.isnan(Q.v).any())
-        out.append(Q)
+def test_interp_depth7_matches_oracle(le, ctx, oracle, kernel):
+    """Cell depth 7 in 3-D: the second launch covers Q columns 4, 5, 6 of 7 -- three components
+    with first > 0, which none of DEPTHS gives (5: one, 9: four and one)."""
+    depth = 7
+    c = dev_case(kernel, 3, "cell", f"d7{kernel}")
+    u = Eul(c.geom, "cell", depth, np.random.default_rng(11 + depth))
+    Q = Lag(c.M, depth)
+    m = le.Markers(ctx).bin(c.geom, kernel, c.Xd, c.idd, c.xsd)
+    le.interp(ctx, m, kernel, "cell", c.geom, u.q, Q.v, c.Xd, q_depth=depth)
+    ctx.synchronize()
     u.unchanged()
-    assert torch.equal(out[0].full, out[1].full)
-    assert len({out[0].v[:, k].cpu().numpy().tobytes() for k in range(Qd)}) == Qd
+    check_interp(oracle, kernel, "cell", c, u.numpy(), Q, depth)
 
 
 # --------------------------------------------------------------------------

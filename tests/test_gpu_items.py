@@ -92,3 +92,16 @@ def test_item_settings_do_not_change_results(le, kind):
         for a in range(3):
             d = np.abs(runs[0][a].cpu().numpy() - fo[a]).max() / np.abs(fo[a]).max()
             assert d <= 1e-12, (st, a, d)
+
+
+def test_removed_tuning_keys_are_unknown(le):
+    """"interp3" and "side_gather" named paths that are gone: they fail as any unknown key does
+    (IBTK_LE_ERR_ARG); "f_stream" -1, the in-line gather the default is compared with, stays."""
+    from ibamr_amd._lib import IBTKLEError
+    ctx = le.Context(0)
+    for key in ("interp3", "side_gather"):
+        with pytest.raises(IBTKLEError) as e:
+            ctx.tune(key, 1)
+        assert e.value.code == 4, key  # IBTK_LE_ERR_ARG
+        assert "unknown tuning key" in str(e.value)
+    ctx.tune("f_stream", -1)

@@ -201,6 +201,40 @@ def test_bitwise_against_oracle_ib_side(le, ctx, oracle, kernel):
         assert np.abs(ga - uc[a]).max() <= SPREAD_TOL * np.abs(uc[a]).max(), f"comp {a} vs caller order"
 
 
+def test_interp_index_list_with_images_matches_oracle(le, ctx, oracle):
+    """3-D side interp of a periodic ghost-box list (markers near the faces listed again,
+    shifted): the Q row of a marker named twice comes from its last entry, as in the oracle's
+    sequential loop.  The ghost points hold values of their own, not their periodic images',
+    so an image entry's sum differs from its marker's unshifted one."""
+    kernel = "IB_4"
+    g = oracle.min_ghost_width(kernel)
+    from ibamr_amd.le import Geometry
+    geom = Geometry.periodic_unit([24, 20, 28], g)
+    rng = np.random.default_rng(3)
+    M = 3000
+    X = rng.uniform(0.0, 1.0, (M, 3))
+    idx, xs, _ = oracle.periodic_index_list(X, geom.x_lower, [1.0, 1.0, 1.0], geom.dx, geom.ilower, geom.iupper, g)
+    idx = idx.astype(np.int32)
+    assert idx.size > M + 1000 and np.unique(idx).size == M
+    q = geom.alloc("side")
+    for a in q:
+        a.copy_(torch.from_numpy(rng.standard_normal(tuple(a.shape))))
+    u0 = [a.cpu().numpy().copy() for a in q]
+    Xd = torch.from_numpy(X).cuda()
+    m = le.Markers(ctx).bin(geom, kernel, Xd, torch.from_numpy(idx).cuda(), torch.from_numpy(xs).cuda())
+    Q = torch.full((M, 3), np.nan, dtype=torch.float64, device="cuda:0")
+    le.interp(ctx, m, kernel, "side", geom, q, Q, Xd)
+    ctx.synchronize()
+    Qo = np.zeros((M, 3))
+    oracle.side_interp(kernel, geom.dx, geom.x_lower, geom.ilower, geom.iupper, geom.gcw, u0, idx, xs, X, Qo)
+    first = np.zeros((M, 3))  # what the first entry of each marker would give
+    _, at = np.unique(idx, return_index=True)
+    oracle.side_interp(kernel, geom.dx, geom.x_lower, geom.ilower, geom.iupper, geom.gcw, u0, idx[at], xs[at], X, first)
+    assert (np.abs(first - Qo).max(axis=1) > 1e-3).sum() > 500, "the images must tell the last entry from the first"
+    err = rel_err(Q.cpu().numpy(), Qo)
+    assert err <= INTERP_TOL, f"interp rel err {err:.3e}"
+
+
 def test_spread_bit_stable_run_to_run(le, ctx):
     """Same inputs, two runs (and a re-bin in between): identical bits."""
     from ibamr_amd.le import Geometry

@@ -417,34 +417,7 @@ def test_cluster_halves(le, oracle, kernel):
 
 
 # --------------------------------------------------------------------------
-# 6: the three-component interp kernel
-# --------------------------------------------------------------------------
-@pytest.mark.parametrize("kernel", ["IB_4", "BSPLINE_4"])
-def test_interp3_halves(le, kernel):
-    """k_interp3 (tune interp3 = 1) under every window, cut and uncut: properties 1 and 2, and
-    the per-component kernel's bits."""
-    case = Case(wc.marker_deep(kernel))
-    cs = case.cs
-    geom = dev_geom(le, cs.geom)
-    q, _ = random_arrays(geom, "side", 1, 25)
-    plain = le.Context(0)
-    m = le.Markers(plain).bin(geom, kernel, case.Xd, case.idd, case.xsd)
-    (Qref,) = interp_modes(le, plain, m, kernel, "side", geom, q, 1, case.Xd, (0, -1), modes=(0,))
-    plain.synchronize()
-    ctx = le.Context(0)
-    ctx.tune("interp3", 1)
-    for cut in (True, False):
-        m = None
-        for name, win in wc.windows(cs.geom).items():
-            if cut or m is None:
-                m = window_table(le, ctx, case, kernel, geom, win, cut)
-            check_interp_window(le, ctx, m, case, kernel, "side", geom, q, 1, win, name, cut,
-                                f"interp3 {kernel} {'cut' if cut else 'uncut'} {name}{win}", Qref)
-    ctx.synchronize()
-
-
-# --------------------------------------------------------------------------
-# 7: a re-binning after the window changed
+# 6: a re-binning after the window changed
 # --------------------------------------------------------------------------
 @pytest.mark.parametrize("kernel", c3.PATHS)
 def test_rebin_after_window_change(le, kernel):

@@ -9,7 +9,7 @@ for v in "$@"; do
   if [ "$v" = default ]; then lib=ibamr_amd/lib/libibtk_le.so; else lib=ibamr_amd/lib/var/$v/libibtk_le.so; fi
   for cfg in ${CFGS:-cfg4 cfg5}; do
     d=$out/${v}_$cfg
-    IBTK_LE_LIB=$PWD/$lib timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $d -o run -- python3 bench.py --config $cfg --move --steps 8 --warmup 2 --no-cpu-baseline --tune side_gather=-1 > $d.log 2>&1 || { echo "$v $cfg failed"; tail -3 $d.log; exit 1; }
+    IBTK_LE_LIB=$PWD/$lib timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $d -o run -- python3 bench.py --config $cfg --move --steps 8 --warmup 2 --no-cpu-baseline > $d.log 2>&1 || { echo "$v $cfg failed"; tail -3 $d.log; exit 1; }
     f=$(find $d -name "*kernel_stats.csv" | head -1)
     python3 -c "
 import csv

@@ -30,7 +30,6 @@ run cfg3_IB_4_W8 --config cfg3 --kernel IB_4_W8
 run cfg3_IB_4 --config cfg3 --kernel IB_4
 run cfg4_random --config cfg4 --marker-order random
 run cfg4_move --config cfg4 --move
-run cfg4_interp3 --config cfg4 --tune interp3=1
 run cfg5 --config cfg5
 run cfg5_move --config cfg5 --move
 run cfg5_move_r10 --config cfg5 --move --regrid-every 10
