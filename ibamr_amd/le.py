@@ -480,11 +480,15 @@ class Level:
 
     @classmethod
     def from_flat(cls, ctx: Context, geoms: Sequence[Geometry], kernel: str, X: torch.Tensor, indices: torch.Tensor,
-                  xshift: Optional[torch.Tensor], offsets: Sequence[int]):
-        """A level from the concatenated lists: patch q's entries are [offsets[q], offsets[q+1])."""
+                  xshift: Optional[torch.Tensor], offsets: Sequence[int], markers: Optional[Markers] = None):
+        """A level from the concatenated lists: patch q's entries are [offsets[q], offsets[q+1]).
+        `markers`: an existing handle of `ctx` to bin the level into (the one handle a patch
+        level keeps across regrids) instead of a new one."""
         self = cls.__new__(cls)
         self.ctx, self.geoms, self.kernel = ctx, list(geoms), kernel
-        self.markers = Markers(ctx)
+        if markers is not None and markers.ctx is not ctx:
+            raise ValueError("markers belong to another context")
+        self.markers = markers if markers is not None else Markers(ctx)
         self.indices = indices.to(torch.int32).contiguous()
         self.xshift = xshift.contiguous() if xshift is not None else None
         self._G = (PatchGeom * len(geoms))(*[g.c for g in geoms])

@@ -1,0 +1,542 @@
+"""GPU: a reused Markers / Level handle gives the bits of a fresh one (history independence).
+
+IBAMR keeps one handle per patch level for a whole run and bins it again after every regrid:
+another list length, other boxes, other lists, and one Context serves several handles.  The
+handle carries some twenty pieces of derived state that outlive a binning (the candidate
+stream and its flags, the re-binning's counts and parities, the item table's signature, the
+duplicate map, the interior selection, host mirrors of device tables), each invalidated by
+hand at three entry points.  The property held here: after any sequence of calls, every array
+an interp, spread, zero_spread, zero_ghosts_spread or fill_interp writes, Markers.order() and
+Markers.count() are bit for bit (torch.equal) what a fresh Context and a fresh handle give
+that saw only the last binning and the same final call -- ibtk_le.h's own promise that a
+spread's order depends on the binning alone.
+
+Inputs and the scripted sequences are tests/reuse_cases.py's; tests/test_reuse_cases_cpu.py
+asserts that consecutive states differ, so a handle that kept its previous state is seen.
+After each state of a sequence, not only the last, the calls are compared with a fresh handle.
+To keep "fresh" honest the last state of every sequence is also held to the C oracle: interp
+bit for bit, spread within SPREAD_TOL = 1e-12 of max |f_ref| with the list fed in
+Markers.order() (the levels: in list order, as test_gpu_spread_fstream.test_level has it).
+"""
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+pytestmark = pytest.mark.gpu
+
+import reuse_cases as rc  # noqa: E402
+
+SENT = 7.0  # Q rows no entry names keep it
+
+
+@pytest.fixture(scope="module")
+def le():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from ibamr_amd import le as _le
+    return _le
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+class Env:
+    """the cases on the device, uploaded once; F's tensors are rewritten in place per state"""
+
+    def __init__(self, le):
+        self.le = le
+        self._geom, self._X, self._u, self._dups, self.F = {}, {}, {}, {}, {}
+        self.n_dev = {"counted": torch.tensor([rc.N_COUNTED], dtype=torch.int32, device="cuda"),
+                      "counted0": torch.tensor([0], dtype=torch.int32, device="cuda")}
+
+    def geom(self, name):
+        if name not in self._geom:
+            p = rc.patch(name)
+            self._geom[name] = self.le.Geometry(list(p.ilower), list(p.iupper), p.g, list(p.dx), list(p.x_lower))
+        return self._geom[name]
+
+    def X(self, st):
+        key = (st.geom, st.X)
+        if key not in self._X:
+            self._X[key] = dev(rc.state_X(st))
+        return self._X[key]
+
+    def u(self, geom, centering, depth):
+        key = (geom, centering, depth)
+        if key not in self._u:
+            self._u[key] = [dev(a) for a in rc.fields(geom, centering, depth)]
+        return self._u[key]
+
+    def dups(self, geom):
+        if geom not in self._dups:
+            idx, xs = rc.dup_list(geom)
+            self._dups[geom] = (dev(idx), dev(xs))
+        return self._dups[geom]
+
+    def set_F(self, st, cols):
+        """the state's F written over the last state's, in place"""
+        if cols not in self.F:
+            self.F[cols] = torch.empty((rc.M, cols), dtype=torch.float64, device="cuda")
+        self.F[cols].copy_(dev(rc.lag_values(st.F, cols)))
+        return self.F[cols]
+
+
+@pytest.fixture(scope="module")
+def env(le):
+    return Env(le)
+
+
+def bin_state(env, m, st):
+    g, X = env.geom(st.geom), env.X(st)
+    if st.lst == "big":
+        m.bin(g, st.kernel, X)
+    elif st.lst == "small":
+        m.bin(g, st.kernel, X, n=rc.N_SMALL)
+    elif st.lst == "empty":
+        m.bin(g, st.kernel, X, n=0)
+    elif st.lst == "dups":
+        m.bin(g, st.kernel, X, *env.dups(st.geom))
+    else:
+        m.bin_count(g, st.kernel, X, env.n_dev[st.lst])
+    return m
+
+
+def calls(env, ctx, m, st, ops, extra=()):
+    """The calls of one state on (ctx, m): {name: tensors}.  ops: "interp", "spread" (side
+    data) and "fused" (zero_spread into NaN, zero_ghosts_spread into 1.5, fill_interp from a
+    copy of u), in that order; extra: the further centrings, interp and spread each."""
+    le, g, X = env.le, env.geom(st.geom), env.X(st)
+    nd = g.ndim
+    out = {}
+    for op in ops:
+        F = env.F[nd]
+        if op == "interp":
+            Q = torch.full((rc.M, nd), SENT, dtype=torch.float64, device="cuda")
+            le.interp(ctx, m, st.kernel, "side", g, env.u(st.geom, "side", 1), Q, X)
+            out["interp"] = [Q]
+        elif op == "spread":
+            f = g.alloc("side")
+            le.spread(ctx, m, st.kernel, "side", g, f, F, X)
+            out["spread"] = f
+        else:
+            f = g.alloc("side", fill=float("nan"))
+            le.zero_spread(ctx, m, st.kernel, "side", g, f, F, X)
+            out["zero_spread"] = f
+            f = g.alloc("side", fill=1.5)
+            le.zero_ghosts_spread(ctx, m, st.kernel, "side", g, f, F, X)
+            out["zero_ghosts_spread"] = f
+            u = [a.clone() for a in env.u(st.geom, "side", 1)]
+            Q = torch.full((rc.M, nd), SENT, dtype=torch.float64, device="cuda")
+            le.fill_interp(ctx, m, st.kernel, "side", g, u, Q, X, periodic=[1] * nd)
+            out["fill_interp"] = [Q] + u
+    for x in extra:
+        centering, depth = rc.EXTRA[x]
+        if "spread" in ops:
+            f = g.alloc(centering, depth=depth)
+            le.spread(ctx, m, st.kernel, centering, g, f, env.F[depth], X, q_depth=depth)
+            out[f"spread {x}"] = f
+        if "interp" in ops:
+            Q = torch.full((rc.M, depth), SENT, dtype=torch.float64, device="cuda")
+            le.interp(ctx, m, st.kernel, centering, g, env.u(st.geom, centering, depth), Q, X, q_depth=depth)
+            out[f"interp {x}"] = [Q]
+    ctx.synchronize()
+    out["order"] = [m.order()]
+    out["count"] = m.count()
+    return out
+
+
+def same(got, want, what):
+    assert got.keys() == want.keys()
+    for k in got:
+        if k == "count":
+            assert got[k] == want[k], f"{what}: count {got[k]} != {want[k]}"
+            continue
+        assert len(got[k]) == len(want[k])
+        for i, (a, b) in enumerate(zip(got[k], want[k])):
+            assert a.shape == b.shape and torch.equal(a, b), f"{what}: {k}[{i}] differs from the fresh handle's"
+
+
+def fresh(env, st, ops, extra=(), setup=None):
+    """the same calls on a fresh Context and a fresh handle that see only the state's binning"""
+    ctx = env.le.Context(0)
+    if setup is not None:
+        setup(ctx)
+    m = bin_state(env, env.le.Markers(ctx), st)
+    out = calls(env, ctx, m, st, ops, extra)
+    m.close()
+    ctx.close()
+    return out
+
+
+WORST = {}  # kernel -> worst spread error against the oracle, printed per test
+
+
+def _rel(got, ref):
+    return float(np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-300))
+
+
+def hold_to_oracle(st, out, extra=()):
+    """a state's (fresh) results against the C oracle: interp bit for bit, rows no entry names
+    untouched; spread within SPREAD_TOL in Markers.order()"""
+    n = rc.entries(st.geom, st.lst)[0].size
+    order = out["order"][0].cpu().numpy()
+    order = order[order < n]
+    assert order.size == n and np.array_equal(np.sort(order), np.arange(n)), "order is not a permutation of the list"
+    todo = [("", "side", 1)] + [(f" {x}",) + rc.EXTRA[x] for x in extra]
+    for tag, centering, depth in todo:
+        if "interp" + tag in out:
+            Qo, named = rc.oracle_interp(st, centering, depth)
+            Q = out["interp" + tag][0].cpu().numpy()
+            assert np.array_equal(Q[named], Qo[named]), f"{st}: interp{tag} is not the oracle's bit for bit"
+            assert np.all(Q[~named] == SENT), f"{st}: interp{tag} wrote a row no entry names"
+        if "spread" + tag in out:
+            fo = rc.oracle_spread(st, centering, depth, order)
+            for a, (got, ref) in enumerate(zip(out["spread" + tag], fo)):
+                if n == 0:
+                    assert not bool(got.any())
+                    continue
+                err = _rel(got.cpu().numpy(), ref)
+                WORST[st.kernel] = max(WORST.get(st.kernel, 0.0), err)
+                print(f"reuse oracle: {st.geom} {st.kernel} {st.lst} {st.X} spread{tag} comp {a}: rel err {err:.2e}")
+                assert err <= rc.SPREAD_TOL, f"{st}: spread{tag} comp {a}: rel err {err:.2e}"
+    print("reuse oracle: worst spread rel err so far " + ", ".join(f"{k} {v:.2e}" for k, v in sorted(WORST.items())))
+
+
+OPS = {"both": ("interp", "spread", "fused"), "interp": ("interp",), "spread": ("spread", "interp")}
+
+
+def set_all_F(env, st):
+    nd = rc.patch(st.geom).ndim
+    for cols in {nd, 1, 2}:
+        env.set_F(st, cols)
+
+
+# --------------------------------------------------------------------------
+# sequences 1-6 and 11: one handle through a scripted sequence
+# --------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(rc.SEQUENCES), ids=str)
+def test_sequence(le, env, name):
+    """1 grow and shrink, 2 kernel change, 3 geometry change, 4 dimension change (IB_4, IB_3,
+    and once with the `dups` list), 5 list kind, 6 re-binning states with no fresh binning in
+    between (IB_4, BSPLINE_4), 11 an empty list in the middle: after every step the handle
+    equals a fresh one binned at that state; the last state's fresh results equal the oracle."""
+    seq = rc.SEQUENCES[name]
+    ctx = le.Context(0)
+    m = le.Markers(ctx)
+    want = None
+    for k, (step, st) in enumerate(zip(seq, rc.states(seq))):
+        set_all_F(env, st)
+        if step.op == "bin":
+            bin_state(env, m, st)
+        else:
+            m.rebin(env.X(st))
+        if step.do == "none":
+            continue
+        got = calls(env, ctx, m, st, OPS[step.do], step.extra)
+        want = fresh(env, st, OPS[step.do], step.extra)
+        same(got, want, f"{name} step {k} ({step.op} {st})")
+        n = rc.entries(st.geom, st.lst)[0].size
+        if st.lst in ("counted", "counted0"):
+            assert got["count"] == rc.M  # the capacity; the rows past the device count are swept by no item
+        else:
+            assert got["count"] == n
+    hold_to_oracle(st, want, step.extra)
+    m.close()
+    ctx.close()
+
+
+# --------------------------------------------------------------------------
+# sequence 7: settings between calls on a standing stream
+# --------------------------------------------------------------------------
+ST7 = rc.State("A3", "IB_4", "big", "X0", 0)
+
+
+def _spread7(env, ctx, m, k, setup, what):
+    st = ST7._replace(F=k)
+    set_all_F(env, st)
+    got = calls(env, ctx, m, st, ("spread", "interp"), ("node",))
+    want = fresh(env, st, ("spread", "interp"), ("node",), setup)
+    same(got, want, what)
+    return st, want
+
+
+@pytest.mark.parametrize("rebins", [0, 1, 2])
+def test_settings_f_stream(le, env, rebins):
+    """f_stream -1: bin, spread (a stream without source rows), `rebins` times rebin(X0) with a
+    spread between two of them; f_stream 1: the spread needs the rows, so the stream is rebuilt;
+    -1 again.  0: the stream stands as built (cand_stream_built).  1: the issue's order -- the
+    first re-binning after a binning has no earlier shifted-z parities to compare with and the
+    stream is rebuilt whatever it holds.  2: the second one moved nothing and flipped nothing,
+    so the stream would be kept on the device (cand_stream's `keep`) if it held the rows.
+    Before all that the handle spreads once under f_stream 1 at other positions, so that it
+    holds source rows of another order: a stream wrongly taken to hold them reads those."""
+    ctx = le.Context(0)
+    first = ST7._replace(X="X_moved", F=9)
+    m = bin_state(env, le.Markers(ctx), first)
+    set_all_F(env, first)
+    same(calls(env, ctx, m, first, ("spread",)), fresh(env, first, ("spread",)), "f_stream default")
+    ctx.tune("f_stream", -1)
+    bin_state(env, m, ST7)
+    _spread7(env, ctx, m, 0, lambda c: c.tune("f_stream", -1), "f_stream -1 after bin")
+    for k in range(rebins):
+        if k:
+            _spread7(env, ctx, m, 3 + k, lambda c: c.tune("f_stream", -1), "f_stream -1 after a re-binning")
+        m.rebin(env.X(ST7))
+    ctx.tune("f_stream", 1)
+    _spread7(env, ctx, m, 1, lambda c: c.tune("f_stream", 1), "f_stream 1 on a stream without source rows")
+    ctx.tune("f_stream", -1)
+    st, want = _spread7(env, ctx, m, 2, lambda c: c.tune("f_stream", -1), "f_stream -1 again")
+    hold_to_oracle(st, want, ("node",))
+
+
+def test_settings_plane_window(le, env):
+    """A mode-0 window cuts the item table of later binnings at its faces: set before a bin
+    and cleared before rebin(X0), and set between a bin and a rebin(X0) -- the re-binning
+    moves nothing, and must still rebuild the table (items_sig)."""
+    zlo = rc.patch("A3").ilower[2] + 5
+    win = (0, zlo, zlo + 7)
+    ctx = le.Context(0)
+    ctx.set_plane_window(*win)
+    m = bin_state(env, le.Markers(ctx), ST7)
+    _spread7(env, ctx, m, 0, lambda c: c.set_plane_window(*win), "window set before bin")
+    ctx.set_plane_window(0, 0, -1)
+    m.rebin(env.X(ST7))
+    _spread7(env, ctx, m, 1, None, "window cleared before rebin")
+    ctx.set_plane_window(*win)
+    m.rebin(env.X(ST7))
+    st, want = _spread7(env, ctx, m, 2, lambda c: c.set_plane_window(*win), "window set before rebin")
+    hold_to_oracle(st, want, ("node",))
+
+
+def test_settings_seg_items(le, env):
+    """seg_items changed between a bin and a rebin: the table keeps the binning's segment
+    length, so the re-binned handle equals a fresh one binned under the old setting; the next
+    bin takes the new one."""
+    ctx = le.Context(0)
+    ctx.tune("seg_items", 1)        # one segment: the whole patch
+    m = bin_state(env, le.Markers(ctx), ST7)
+    _spread7(env, ctx, m, 0, lambda c: c.tune("seg_items", 1), "seg_items 1")
+    ctx.tune("seg_items", 100000)   # the shortest segments
+    moved = ST7._replace(X="X_moved", F=1)
+    m.rebin(env.X(moved))
+    set_all_F(env, moved)
+    got = calls(env, ctx, m, moved, ("spread", "interp"), ("node",))
+    same(got, fresh(env, moved, ("spread", "interp"), ("node",), lambda c: c.tune("seg_items", 1)),
+         "rebin after seg_items changed")
+    bin_state(env, m, ST7)
+    st, want = _spread7(env, ctx, m, 2, lambda c: c.tune("seg_items", 100000), "bin under the new seg_items")
+    hold_to_oracle(st, want, ("node",))
+
+
+# --------------------------------------------------------------------------
+# levels
+# --------------------------------------------------------------------------
+class Lvl:
+    """a level case on the device"""
+
+    def __init__(self, le, name):
+        c = self.c = rc.level(name)
+        self.name = name
+        self.geoms = c.geoms(le)
+        self.X = {"X0": dev(c.X), "X_moved": dev(c.X_moved)}
+        self.ghost = (dev(c.gh_idx), dev(c.gh_xs), [int(v) for v in c.gh_off])
+        self.interior = (dev(c.int_idx), [int(v) for v in c.int_off])
+        self.u = [[dev(a) for a in per] for per in c.u]
+        self.tiled = name != "LB"  # equal patches that tile a box: fill_interp allowed
+
+    def make(self, le, ctx, X, markers=None, lists=None):
+        return le.Level.from_flat(ctx, self.geoms, rc.LEVEL_KERNEL, self.X[X], *(lists or self.ghost), markers=markers)
+
+
+@pytest.fixture(scope="module")
+def levels(le):
+    cache = {}
+
+    def get(name):
+        if name not in cache:
+            cache[name] = Lvl(le, name)
+        return cache[name]
+    return get
+
+
+def level_calls(le, L, lvl, X, F, select=None, plain=True):
+    """interp, spread, zero_spread, fill_interp where the level allows it, then the interior
+    selection's interp, of level handle `lvl` at positions L.X[X]"""
+    Xd = L.X[X]
+    out = {}
+    if plain:
+        Q = torch.full((rc.M, 3), SENT, dtype=torch.float64, device="cuda")
+        lvl.interp("side", L.u, Q, Xd)
+        out["interp"] = [Q]
+        f = [g.alloc("side") for g in L.geoms]  # freshly allocated at every state
+        lvl.spread("side", f, F, Xd)
+        out["spread"] = [a for per in f for a in per]
+        f = [g.alloc("side", fill=float("nan")) for g in L.geoms]
+        lvl.zero_spread("side", f, F, Xd)
+        out["zero_spread"] = [a for per in f for a in per]
+        if L.tiled:
+            u = le.alloc_level(L.geoms, "side")
+            for per, src in zip(u, L.u):
+                for a, b in zip(per, src):
+                    a.copy_(b)
+            Q = torch.full((rc.M, 3), SENT, dtype=torch.float64, device="cuda")
+            lvl.fill_interp("side", u, Q, Xd, periodic=[1, 1, 1])
+            out["fill_interp"] = [Q] + [a for per in u for a in per]
+    idx, off = select or L.interior
+    lvl.select_interior(rc.M, idx, off)
+    Q = torch.full((rc.M, 3), SENT, dtype=torch.float64, device="cuda")
+    lvl.interp("side", L.u, Q, Xd)
+    out["interp selected"] = [Q]
+    lvl.ctx.synchronize()
+    out["order"] = [lvl.markers.order()]
+    out["count"] = lvl.markers.count()
+    return out
+
+
+def level_fresh(le, L, X, F, lists=None, select=None, plain=True):
+    ctx = le.Context(0)
+    lvl = L.make(le, ctx, X, lists=lists)
+    out = level_calls(le, L, lvl, X, F, select, plain)
+    lvl.markers.close()
+    ctx.close()
+    return out
+
+
+def level_oracle_check(L, X, seed, out):
+    c = L.c
+    Qo, fo = rc.level_oracle(c, X, rc.lag_values(seed, 3))
+    Q = out["interp selected"][0].cpu().numpy()
+    named = np.zeros(rc.M, bool)
+    named[c.int_idx] = True
+    assert np.array_equal(Q[named], Qo[named]), f"{L.name} {X}: the selection's interp is not the oracle's"
+    assert np.all(Q[~named] == SENT)
+    for q in range(c.npatch):
+        for a in range(3):
+            err = _rel(out["spread"][3 * q + a].cpu().numpy(), fo[q][a])
+            WORST["IB_4 (level)"] = max(WORST.get("IB_4 (level)", 0.0), err)
+            assert err <= rc.SPREAD_TOL, f"{L.name} {X} patch {q} comp {a}: spread rel err {err:.2e}"
+    print(f"reuse oracle: level {L.name} {X}: worst spread rel err so far {WORST['IB_4 (level)']:.2e}")
+
+
+def test_patch_and_level_on_one_handle(le, env, levels):
+    """8. Markers.bin(A3) -> level LA -> Markers.bin(A3) -> level LB -> level LA -> level LC on
+    one handle.  LA and LB have four patches each, so each takes over the other's patch table
+    and its host mirror; the spread arrays are new at every state.  The single-patch calls are
+    refused while the handle holds a level, and the level calls while it holds a patch."""
+    from ibamr_amd._lib import IBTKLEError
+    ctx = le.Context(0)
+    m = le.Markers(ctx)
+    F3 = env.F.setdefault(3, torch.empty((rc.M, 3), dtype=torch.float64, device="cuda"))
+    gA = env.geom("A3")
+    Qj = torch.full((rc.M, 3), SENT, dtype=torch.float64, device="cuda")
+    script = [("patch", "X0"), ("LA", "X0"), ("patch", "X_moved"), ("LB", "X0"), ("LA", "X_moved"), ("LC", "X0")]
+    lvl = None
+    for k, (what, X) in enumerate(script):
+        if what == "patch":
+            st = rc.State("A3", "IB_4", "big", X, k)
+            set_all_F(env, st)
+            bin_state(env, m, st)
+            same(calls(env, ctx, m, st, OPS["both"]), fresh(env, st, OPS["both"]), f"step {k}: patch after a level")
+            if lvl is not None:
+                with pytest.raises(IBTKLEError, match="not binned for a level"):
+                    lvl.interp("side", levels("LA").u, Qj, levels("LA").X["X0"])
+                with pytest.raises(IBTKLEError, match="not binned for a level"):
+                    lvl.spread("side", [g.alloc("side") for g in lvl.geoms], F3, levels("LA").X["X0"])
+            continue
+        L = levels(what)
+        F3.copy_(dev(rc.lag_values(k, 3)))
+        lvl = L.make(le, ctx, X, markers=m)
+        assert lvl.markers is m
+        got = level_calls(le, L, lvl, X, F3)
+        want = level_fresh(le, L, X, F3)
+        same(got, want, f"step {k}: level {what} at {X}")
+        level_oracle_check(L, X, k, want)
+        with pytest.raises(IBTKLEError, match="binned for a level"):
+            le.interp(ctx, m, "IB_4", "side", gA, env.u("A3", "side", 1), Qj, env.X(rc.State("A3", "IB_4", "big", "X0", 0)))
+        with pytest.raises(IBTKLEError, match="binned for a level"):
+            le.spread(ctx, m, "IB_4", "side", gA, gA.alloc("side"), F3, env.X(rc.State("A3", "IB_4", "big", "X0", 0)))
+    ctx.synchronize()
+    assert bool((Qj == SENT).all()), "a refused call wrote Q"
+
+
+def test_interior_selection_across_binnings(le, env, levels):
+    """9. LA: select_interior, interp; a full Level.bin(X_moved); select_interior with the
+    same tensor object (the wrapper keeps it, the library must not keep its selection);
+    interp; then relist to other lists with the same number of offsets, bin, select again."""
+    L = levels("LA")
+    c = L.c
+    F3 = env.F.setdefault(3, torch.empty((rc.M, 3), dtype=torch.float64, device="cuda"))
+    F3.copy_(dev(rc.lag_values(0, 3)))
+    ctx = le.Context(0)
+    lvl = L.make(le, ctx, "X0")
+    same(level_calls(le, L, lvl, "X0", F3, plain=False), level_fresh(le, L, "X0", F3, plain=False), "first selection")
+    lvl.bin(L.X["X_moved"])
+    got = level_calls(le, L, lvl, "X_moved", F3, plain=False)   # L.interior[0]: the same tensor object
+    want = level_fresh(le, L, "X_moved", F3, plain=False)
+    same(got, want, "the same interior list after a full binning")
+    Qo, _ = rc.level_oracle(c, "X_moved", rc.lag_values(0, 3))
+    named = np.zeros(rc.M, bool)
+    named[c.int_idx] = True
+    assert np.array_equal(want["interp selected"][0].cpu().numpy()[named], Qo[named])
+    gi, gx, go, ii, io = rc.relisted(c)
+    lists, sel = (dev(gi), dev(gx), go), (dev(ii), io)
+    lvl.relist(*lists).bin(L.X["X0"])
+    got = level_calls(le, L, lvl, "X0", F3, select=sel)
+    want = level_fresh(le, L, "X0", F3, lists=lists, select=sel)
+    same(got, want, "relisted, binned, selected again")
+    Q = want["interp selected"][0].cpu().numpy()
+    for q in range(c.npatch):
+        idx = ii[io[q]:io[q + 1]]
+        Qr = np.zeros((rc.M, 3))
+        c.oracle("interp", q, "side", c.u[q], idx, np.zeros((idx.size, 3)), Qr, X=c.X)
+        assert np.array_equal(Q[idx], Qr[idx]), f"patch {q}: the relisted selection's interp is not the oracle's"
+    named[:] = False
+    named[ii] = True
+    assert np.all(Q[~named] == SENT)
+
+
+def test_handles_share_a_context(le, env, levels):
+    """10. m1 (A3, IB_4, big), m2 (B3, IB_6, dups), m3 (A2) and level LA on one Context, which
+    lends them all its sort keys, scan storage, gathered F, counters and level tables, their
+    calls interleaved: every output equals the same call on a private fresh context."""
+    ctx = le.Context(0)
+    L = levels("LA")
+    F3 = env.F.setdefault(3, torch.empty((rc.M, 3), dtype=torch.float64, device="cuda"))
+    s1 = rc.State("A3", "IB_4", "big", "X0", 1)
+    s2 = rc.State("B3", "IB_6", "dups", "X0", 2)
+    s3 = rc.State("A2", "IB_4", "big", "X0", 3)
+    step = [0]
+
+    def check(m, st, ops, what):
+        step[0] += 1
+        st = st._replace(F=10 + step[0])
+        set_all_F(env, st)
+        same(calls(env, ctx, m, st, ops), fresh(env, st, ops), what)
+        return st
+
+    m1 = bin_state(env, le.Markers(ctx), s1)
+    m2 = bin_state(env, le.Markers(ctx), s2)
+    m3 = bin_state(env, le.Markers(ctx), s3)
+    lvl = L.make(le, ctx, "X0")
+    check(m1, s1, ("spread",), "spread m1")
+    s2 = s2._replace(X="X_moved")
+    m2.rebin(env.X(s2))
+    F3.copy_(dev(rc.lag_values(20, 3)))
+    same(level_calls(le, L, lvl, "X0", F3), level_fresh(le, L, "X0", F3), "level spread")
+    check(m1, s1, ("interp",), "interp m1")
+    s1 = s1._replace(X="X_moved")
+    m1.rebin(env.X(s1))
+    check(m3, s3, ("spread", "interp"), "2-D spread m3")
+    last2 = check(m2, s2, ("spread", "interp"), "spread m2")
+    want2 = fresh(env, last2, ("spread", "interp"))
+    m2.close()
+    last1 = check(m1, s1, ("spread", "interp"), "spread m1 after m2 closed")
+    hold_to_oracle(last1, fresh(env, last1, ("spread", "interp")))
+    hold_to_oracle(last2, want2)
+    F3.copy_(dev(rc.lag_values(21, 3)))
+    lvl.rebin(L.X["X_moved"])  # (and the selection made above goes with the order it was made for)
+    want = level_fresh(le, L, "X_moved", F3)
+    same(level_calls(le, L, lvl, "X_moved", F3), want, "level re-binned after the others")
+    level_oracle_check(L, "X_moved", 21, want)
