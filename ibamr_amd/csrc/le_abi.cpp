@@ -178,7 +178,7 @@ struct ibtk_le_markers_s {
     ColGeom cg{};        // 3-D: column binning (le_sweep.hip)
     int S = 0, nseg = 0;  // 3-D: sweep segments
     ibtk_le_patch_geom geom{};
-    DevBuf sorted_key, sorted_l, sorted_s, sorted_X, sorted_a, plane_start, indices, xshift;
+    DevBuf sorted_key, sorted_l, sorted_s, sorted_X, plane_start, indices, xshift;
     // 3-D: the sorted positions are sorted_X or sorted_X2, the one the device cell xcur
     // names (ibtk_le_markers_rebin swaps them on the device); xcur_set once it is written
     DevBuf sorted_X2, xcur;
@@ -584,8 +584,8 @@ extern "C" int ibtk_le_markers_destroy(ibtk_le_markers m) {
     hipStreamSynchronize(m->ctx->stream);
     for (DevBuf* b : {&m->sorted_X2, &m->xcur, &m->lvl_nbr})
         b->release();
-    for (DevBuf* b : {&m->sorted_key, &m->sorted_l, &m->sorted_s, &m->sorted_X, &m->sorted_a, &m->plane_start, &m->indices,
-                      &m->xshift, &m->cand_cnt, &m->cand_off, &m->cand_idx, &m->last, &m->qdst, &m->items,
+    for (DevBuf* b : {&m->sorted_key, &m->sorted_l, &m->sorted_s, &m->sorted_X, &m->plane_start, &m->indices, &m->xshift,
+                      &m->cand_cnt, &m->cand_off, &m->cand_idx, &m->last, &m->qdst, &m->items,
                       &m->nsub, &m->isub, &m->nitems, &m->pd, &m->entry_off, &m->qin, &m->owner, &m->int_off,
                       &m->rb_cin, &m->rb_cout, &m->rb_d, &m->rb_mstart, &m->rb_ps2, &m->rb_mbits,
                       &m->rb_wcnt, &m->rb_wpre, &m->rb_mlist, &m->rb_scr, &m->rb_big, &m->rb_nbig, &m->cs_cnt,
@@ -600,6 +600,28 @@ extern "C" int ibtk_le_markers_count(ibtk_le_markers m) { return m ? m->n : -1; 
 extern "C" int ibtk_le_markers_order(ibtk_le_markers m, const int** order_dev) {
     if (!m || !order_dev) return fail(IBTK_LE_ERR_ARG, "markers_order: null argument");
     *order_dev = m->sorted_l.as<int>();
+    return IBTK_LE_OK;
+}
+
+// exclusive prefix sums on the context stream (rocPRIM), temp storage grown as needed
+static int scan_excl(ibtk_le_ctx ctx, const int* in, int* out, int n) {
+    size_t tb = 0;
+    HIP_TRY(launch_scan(nullptr, tb, in, out, n, ctx->stream));
+    if (int rc = ctx->temp.ensure(tb)) return rc;
+    tb = ctx->temp.cap;
+    HIP_TRY(launch_scan(ctx->temp.p, tb, in, out, n, ctx->stream));
+    return IBTK_LE_OK;
+}
+
+// Stable sort of (keys, vals) on the context stream: out_keys/out_vals may be
+// scratch of the caller; uses ctx->temp.
+static int sort_pairs(ibtk_le_ctx ctx, const unsigned* kin, unsigned* kout, const int* vin, int* vout, int n,
+                      int end_bit) {
+    size_t tb = 0;
+    HIP_TRY(launch_sort(nullptr, tb, kin, kout, vin, vout, n, end_bit, ctx->stream));
+    if (int rc = ctx->temp.ensure(tb)) return rc;
+    tb = ctx->temp.cap;
+    HIP_TRY(launch_sort(ctx->temp.p, tb, kin, kout, vin, vout, n, end_bit, ctx->stream));
     return IBTK_LE_OK;
 }
 
@@ -630,8 +652,7 @@ static int build_items(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, const int
     // 7.04e9 -> 6.62e9, profiles/r04q, r04r)
     const int target = ctx->tune.split_target > 0 ? ctx->tune.split_target
                                                   : (m->npatch ? LEVEL_SPLIT_TARGET : IBTK_LE_SPLIT_TARGET);
-    Params p;
-    std::memset(&p, 0, sizeof(p));
+    Params p{};
     if (!m->npatch && ctx->zlo <= ctx->zhi) {
         // cut the items at the plane window's edges, so that the items of a
         // restricted call (ibtk_le_ctx_set_plane_window) are exactly the ones
@@ -689,10 +710,6 @@ static int build_items(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, const int
     return IBTK_LE_OK;
 }
 
-static int markers_bin_impl(ibtk_le_ctx ctx, ibtk_le_markers m, const ibtk_le_patch_geom* geom, int kernel,
-                            const double* X_dev, const int* indices_dev, const double* Xshift_dev, int nindices,
-                            const int* n_dev);
-
 // The sorted entries' marker indices and positions, and the bucket starts: the
 // gather records each non-empty bucket's first entry, a suffix-min scan fills in
 // the empty buckets.
@@ -713,6 +730,170 @@ static int gather_buckets(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, const 
     return IBTK_LE_OK;
 }
 
+// Which event clears which of the handle's caches -- the only place that does:
+//
+//   event                   cand_valid  dedup_done  has_dups  qin_valid  sel_cached
+//   BINNED     a new list       x           x          x          x          x
+//   REBINNED   a new order      x           x          x          x          -
+//   RESELECT   lists rewritten  -           -          -          -          x
+//
+// cand_valid: the 2-D spread's candidate lists (build_candidates); dedup_done / has_dups:
+// the interp's last-entry targets (build_dedup); qin_valid: the level interp's interior
+// targets; sel_cached: the selection they were made from, which stands across a
+// re-binning that moved nothing (sel_gs, decided on the device).  The 3-D candidate
+// stream (cs_state, cs_skip) and the shifted-z parities' state word (zst) follow the
+// bucket starts and are reset where those are settled, in build_items.
+enum CacheEvent { BINNED, REBINNED, RESELECT };
+static void invalidate(ibtk_le_markers m, CacheEvent ev) {
+    if (ev != RESELECT) m->cand_valid = m->dedup_done = m->has_dups = m->qin_valid = false;
+    if (ev != REBINNED) m->sel_cached = false;
+}
+
+// What every launch takes from the handle and the context: the binning's geometry, item
+// table and sorted arrays, the kept lists, the error word and the store sink.  Each caller
+// adds what only it knows (prepare: the plane window and h3; level_params: the components).
+static void handle_params(ibtk_le_ctx ctx, ibtk_le_markers m, const double* X, Params& p) {
+    p.bg = m->bg;
+    p.cg = m->cg;
+    p.S = m->S;
+    p.nseg = m->nseg;
+    p.nbuckets_total = m->nbuckets_total;
+    p.items = m->items.as<SweepItem>();
+    p.nitems = m->nitems.as<int>();
+    p.item_bound = m->item_bound;
+    p.nsorted = m->n;
+    p.X = X;
+    p.indices = m->has_indices ? m->indices.as<int>() : nullptr;
+    p.Xshift = m->has_xshift ? m->xshift.as<double>() : nullptr;
+    p.sorted_l = m->sorted_l.as<int>();
+    p.sorted_s = m->sorted_s.as<int>();
+    p.sorted_X = m->sorted_X.as<double>();
+    p.sorted_X_ref = m->xcur_set ? m->xcur.as<double*>() : nullptr;
+    p.sorted_key = m->sorted_key.as<unsigned>();
+    p.plane_start = m->plane_start.as<int>();
+    p.err = ctx->err.as<int>();
+    p.sink = ctx->sink.as<double>();
+    p.K6 = ib6_K();
+    p.tune = ctx->tune;
+    if (m->npatch) {
+        p.pd = m->pd.as<PatchDesc>();
+        p.npatch = m->npatch;
+        p.entry_off = m->entry_off.as<int>();
+    }
+}
+
+// The front of a binning whose geometry the handle already holds: nstarts bucket starts,
+// the sorted arrays of the m->n entries, the handle's own copy of the lists, and p for the
+// launches.  An empty list gets its (zero) bucket starts and nothing else.
+static int bin_buffers(ibtk_le_ctx ctx, ibtk_le_markers m, const double* X_dev, const int* indices_dev,
+                       const double* Xshift_dev, size_t nstarts, Params& p) {
+    const hipStream_t s = ctx->stream;
+    const size_t n = (size_t)m->n;
+    int rc;
+    if ((rc = m->plane_start.ensure(sizeof(int) * nstarts))) return rc;
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(m->plane_start.p, 0, sizeof(int) * nstarts, s));
+        return IBTK_LE_OK;
+    }
+    if ((rc = m->sorted_key.ensure(sizeof(unsigned) * n))) return rc;
+    if ((rc = m->sorted_l.ensure(sizeof(int) * n))) return rc;
+    if ((rc = m->sorted_s.ensure(sizeof(int) * n))) return rc;
+    if ((rc = m->sorted_X.ensure(sizeof(double) * n * m->ndim))) return rc;
+    if ((rc = ctx->keys_in.ensure(sizeof(unsigned) * n))) return rc;
+    if ((rc = ctx->vals_in.ensure(sizeof(int) * n))) return rc;
+    if (m->has_indices) {
+        if ((rc = m->indices.ensure(sizeof(int) * n))) return rc;
+        if (indices_dev != m->indices.p)  // (a re-binning passes the kept list)
+            HIP_TRY(hipMemcpyAsync(m->indices.p, indices_dev, sizeof(int) * n, hipMemcpyDeviceToDevice, s));
+    }
+    if (m->has_xshift) {
+        const size_t xb = sizeof(double) * n * m->ndim;
+        if ((rc = m->xshift.ensure(xb))) return rc;
+        if (Xshift_dev != m->xshift.p) HIP_TRY(hipMemcpyAsync(m->xshift.p, Xshift_dev, xb, hipMemcpyDeviceToDevice, s));
+    }
+    handle_params(ctx, m, X_dev, p);
+    p.n_dev = m->n_dev;
+    return IBTK_LE_OK;
+}
+
+// The 3-D column binning of one patch or of a level, from the committed handle on: the
+// entries keyed by bucket and sorted (stable: by bucket, then list entry), the sorted
+// arrays and bucket starts gathered, the sweep items built.
+static int bin_columns(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, const double* X_dev, const int* indices_dev,
+                       const double* Xshift_dev) {
+    const int n = m->n, nb = m->nbuckets_total;
+    Params p{};
+    int rc;
+    if ((rc = bin_buffers(ctx, m, X_dev, indices_dev, Xshift_dev, (size_t)nb + 1, p))) return rc;
+    if (n > 0) {
+        HIP_TRY(launch_bin_col(kernel, p, n, ctx->keys_in.as<unsigned>(), ctx->vals_in.as<int>(), ctx->stream));
+        int end_bit = 1;
+        while ((1ULL << end_bit) <= (unsigned long long)nb) ++end_bit;
+        if ((rc = sort_pairs(ctx, ctx->keys_in.as<unsigned>(), m->sorted_key.as<unsigned>(), ctx->vals_in.as<int>(),
+                             m->sorted_l.as<int>(), n, end_bit)))
+            return rc;
+        if ((rc = gather_buckets(ctx, m, kernel, p, n, nb))) return rc;  // gather fused with the bucket starts
+    }
+    return build_items(ctx, m, kernel);
+}
+
+// The 2-D brick binning's tail: keys by brick and cell, the sort, the brick starts, the gather.
+static int bin_bricks(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, const double* X_dev, const int* indices_dev,
+                      const double* Xshift_dev) {
+    const hipStream_t s = ctx->stream;
+    const int n = m->n, nplanes = m->bg.nbricks * BRICK2;
+    Params p{};
+    int rc;
+    if ((rc = bin_buffers(ctx, m, X_dev, indices_dev, Xshift_dev, (size_t)nplanes + 1, p))) return rc;
+    if (n == 0) return IBTK_LE_OK;
+    HIP_TRY(launch_bin(kernel, p, n, ctx->keys_in.as<unsigned>(), ctx->vals_in.as<int>(), s));
+    if ((rc = sort_pairs(ctx, ctx->keys_in.as<unsigned>(), m->sorted_key.as<unsigned>(), ctx->vals_in.as<int>(),
+                         m->sorted_l.as<int>(), n, end_bit_for(m->bg))))
+        return rc;
+    HIP_TRY(launch_brick_start(m->sorted_key.as<unsigned>(), n, nplanes, m->bg.shift - 4,  // 4 = log2(BRICK2)
+                               m->plane_start.as<int>(), s));
+    HIP_TRY(launch_gather_sorted(p, n, m->sorted_s.as<int>(), m->sorted_X.as<double>(), s));
+    return IBTK_LE_OK;
+}
+
+// Validate, then commit, then device work: a call refused before the commit leaves the
+// handle as it was; one that fails after it leaves the handle unbinned (kernel -1).
+static int markers_bin_impl(ibtk_le_ctx ctx, ibtk_le_markers m, const ibtk_le_patch_geom* geom, int kernel,
+                            const double* X_dev, const int* indices_dev, const double* Xshift_dev, int nindices,
+                            const int* n_dev) {
+    if (!ctx || !m) return fail(IBTK_LE_ERR_ARG, "markers_bin: null ctx/markers");
+    if (int rc = check_geom(geom)) return rc;
+    if (kernel < 0 || kernel >= K_COUNT) return fail(IBTK_LE_ERR_UNKNOWN_KERNEL, "Unknown kernel function %d", kernel);
+    if (nindices < 0) return fail(IBTK_LE_ERR_ARG, "negative list length");
+    if (nindices > 0 && !X_dev) return fail(IBTK_LE_ERR_ARG, "null X");
+    if (set_device(ctx)) return IBTK_LE_ERR_DEVICE;
+    BinGeom bg;
+    ColGeom cg{};
+    const bool cols = geom->ndim == 3;
+    if (cols) {
+        if (int rc = make_col_geom(geom, kernel, bg, cg)) return rc;
+    } else {
+        if (int rc = make_bin_geom(geom, kernel, bg)) return rc;
+    }
+    m->n = nindices;
+    m->ndim = geom->ndim;
+    m->bg = bg;
+    m->cg = cg;
+    m->npatch = 0;
+    m->nbuckets_total = cg.nbuckets;
+    if (cols) sweep_segments(cg, m->S, m->nseg, ctx->tune.seg_items, false);
+    m->geom = *geom;
+    m->has_indices = indices_dev != nullptr;
+    m->has_xshift = Xshift_dev != nullptr;
+    m->n_dev = n_dev;
+    m->binned3 = cols;
+    invalidate(m, BINNED);
+    m->kernel = -1;  // until the device phase is through
+    if (int rc = (cols ? bin_columns : bin_bricks)(ctx, m, kernel, X_dev, indices_dev, Xshift_dev)) return rc;
+    m->kernel = kernel;
+    return IBTK_LE_OK;
+}
+
 extern "C" int ibtk_le_markers_bin(ibtk_le_ctx ctx, ibtk_le_markers m, const ibtk_le_patch_geom* geom, int kernel,
                                    const double* X_dev, const int* indices_dev, const double* Xshift_dev,
                                    int nindices) {
@@ -724,16 +905,6 @@ extern "C" int ibtk_le_markers_bin_count(ibtk_le_ctx ctx, ibtk_le_markers m, con
     if (!n_dev) return fail(IBTK_LE_ERR_ARG, "markers_bin_count: null device count");
     if (geom && geom->ndim != 3) return fail(IBTK_LE_ERR_ARG, "markers_bin_count: 3-D patches only");
     return markers_bin_impl(ctx, m, geom, kernel, X_dev, nullptr, nullptr, capacity, n_dev);
-}
-
-// exclusive prefix sums on the context stream (rocPRIM), temp storage grown as needed
-static int scan_excl(ibtk_le_ctx ctx, const int* in, int* out, int n) {
-    size_t tb = 0;
-    HIP_TRY(launch_scan(nullptr, tb, in, out, n, ctx->stream));
-    if (int rc = ctx->temp.ensure(tb)) return rc;
-    tb = ctx->temp.cap;
-    HIP_TRY(launch_scan(ctx->temp.p, tb, in, out, n, ctx->stream));
-    return IBTK_LE_OK;
 }
 
 // The last binning's list re-binned at new positions X_dev: the result -- sorted
@@ -752,10 +923,7 @@ extern "C" int ibtk_le_markers_rebin(ibtk_le_ctx ctx, ibtk_le_markers m, const d
         return markers_bin_impl(ctx, m, &g, m->kernel, X_dev, m->has_indices ? m->indices.as<int>() : nullptr,
                                 m->has_xshift ? m->xshift.as<double>() : nullptr, n, nullptr);
     }
-    m->cand_valid = false;
-    m->dedup_done = false;
-    m->qin_valid = false;
-    m->has_dups = false;
+    invalidate(m, REBINNED);
     if (n == 0) return build_items(ctx, m, m->kernel);
     const hipStream_t s = ctx->stream;
     const int nb = m->nbuckets_total;
@@ -783,20 +951,9 @@ extern "C" int ibtk_le_markers_rebin(ibtk_le_ctx ctx, ibtk_le_markers m, const d
         m->rb_zeroed_nb = nb;
     }
     // (the sentinel word past the last and the movers' long-list queue: cleared by k_rekey)
-    Params p;
-    std::memset(&p, 0, sizeof(p));
-    p.bg = m->bg;
-    p.cg = m->cg;
-    p.nbuckets_total = nb;
-    p.X = X_dev;
-    p.indices = m->has_indices ? m->indices.as<int>() : nullptr;
-    p.Xshift = m->has_xshift ? m->xshift.as<double>() : nullptr;
+    Params p{};
+    handle_params(ctx, m, X_dev, p);
     p.n_dev = m->n_dev;
-    if (m->npatch) {
-        p.pd = m->pd.as<PatchDesc>();
-        p.npatch = m->npatch;
-        p.entry_off = m->entry_off.as<int>();
-    }
     RebinBufs r{};
     r.n = n;
     r.nb = nb;
@@ -848,103 +1005,6 @@ extern "C" int ibtk_le_markers_rebin(ibtk_le_ctx ctx, ibtk_le_markers m, const d
     return build_items(ctx, m, m->kernel, r.wpre + nw);
 }
 
-static int markers_bin_impl(ibtk_le_ctx ctx, ibtk_le_markers m, const ibtk_le_patch_geom* geom, int kernel,
-                            const double* X_dev, const int* indices_dev, const double* Xshift_dev, int nindices,
-                            const int* n_dev) {
-    if (!ctx || !m) return fail(IBTK_LE_ERR_ARG, "markers_bin: null ctx/markers");
-    if (int rc = check_geom(geom)) return rc;
-    if (kernel < 0 || kernel >= K_COUNT) return fail(IBTK_LE_ERR_UNKNOWN_KERNEL, "Unknown kernel function %d", kernel);
-    if (nindices < 0) return fail(IBTK_LE_ERR_ARG, "negative list length");
-    if (nindices > 0 && !X_dev) return fail(IBTK_LE_ERR_ARG, "null X");
-    if (set_device(ctx)) return IBTK_LE_ERR_DEVICE;
-    BinGeom bg;
-    ColGeom cg{};
-    const bool cols = geom->ndim == 3;
-    if (cols) {
-        if (int rc = make_col_geom(geom, kernel, bg, cg)) return rc;
-    } else {
-        if (int rc = make_bin_geom(geom, kernel, bg)) return rc;
-    }
-    const hipStream_t s = ctx->stream;
-    const int n = nindices;
-    m->n = n;
-    m->kernel = kernel;
-    m->ndim = geom->ndim;
-    m->bg = bg;
-    m->cg = cg;
-    m->npatch = 0;
-    m->nbuckets_total = cg.nbuckets;
-    if (cols) sweep_segments(cg, m->S, m->nseg, ctx->tune.seg_items, false);
-    m->geom = *geom;
-    m->has_indices = indices_dev != nullptr;
-    m->has_xshift = Xshift_dev != nullptr;
-    m->cand_valid = false;
-    m->dedup_done = false;
-    m->qin_valid = false;
-    m->sel_cached = false;
-    m->has_dups = false;
-    m->n_dev = n_dev;
-    m->binned3 = cols;
-    int rc = 0;
-    const int nplanes = cols ? cg.nbuckets : bg.nbricks * BRICK2;  // bucket starts: nplanes + 1
-    if ((rc = m->plane_start.ensure(sizeof(int) * (size_t)(nplanes + 1)))) return rc;
-    if (n == 0) {
-        HIP_TRY(hipMemsetAsync(m->plane_start.p, 0, sizeof(int) * (size_t)(nplanes + 1), s));
-        if (cols) return build_items(ctx, m, kernel);
-        return IBTK_LE_OK;
-    }
-    if ((rc = m->sorted_key.ensure(sizeof(unsigned) * (size_t)n))) return rc;
-    if ((rc = m->sorted_l.ensure(sizeof(int) * (size_t)n))) return rc;
-    if ((rc = m->sorted_s.ensure(sizeof(int) * (size_t)n))) return rc;
-    if ((rc = m->sorted_X.ensure(sizeof(double) * (size_t)n * geom->ndim))) return rc;
-    if ((rc = ctx->keys_in.ensure(sizeof(unsigned) * (size_t)n))) return rc;
-    if ((rc = ctx->vals_in.ensure(sizeof(int) * (size_t)n))) return rc;
-    if (m->has_indices) {
-        if ((rc = m->indices.ensure(sizeof(int) * (size_t)n))) return rc;
-        if (indices_dev != m->indices.p)  // (a re-binning passes the kept list)
-            HIP_TRY(hipMemcpyAsync(m->indices.p, indices_dev, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, s));
-    }
-    if (m->has_xshift) {
-        const size_t xb = sizeof(double) * (size_t)n * geom->ndim;
-        if ((rc = m->xshift.ensure(xb))) return rc;
-        if (Xshift_dev != m->xshift.p) HIP_TRY(hipMemcpyAsync(m->xshift.p, Xshift_dev, xb, hipMemcpyDeviceToDevice, s));
-    }
-    Params p;
-    std::memset(&p, 0, sizeof(p));
-    p.bg = bg;
-    p.cg = cg;
-    p.nbuckets_total = cg.nbuckets;
-    p.X = X_dev;
-    p.indices = m->has_indices ? m->indices.as<int>() : nullptr;
-    p.Xshift = m->has_xshift ? m->xshift.as<double>() : nullptr;
-    p.n_dev = n_dev;
-    if (cols) HIP_TRY(launch_bin_col(kernel, p, n, ctx->keys_in.as<unsigned>(), ctx->vals_in.as<int>(), s));
-    else HIP_TRY(launch_bin(kernel, p, n, ctx->keys_in.as<unsigned>(), ctx->vals_in.as<int>(), s));
-    int end_bit = 1;
-    if (cols) {
-        while ((1ULL << end_bit) <= (unsigned long long)cg.nbuckets) ++end_bit;
-    } else {
-        end_bit = end_bit_for(bg);
-    }
-    size_t tb = 0;
-    HIP_TRY(launch_sort(nullptr, tb, ctx->keys_in.as<unsigned>(), m->sorted_key.as<unsigned>(),
-                        ctx->vals_in.as<int>(), m->sorted_l.as<int>(), n, end_bit, s));
-    if ((rc = ctx->temp.ensure(tb))) return rc;
-    tb = ctx->temp.cap;
-    HIP_TRY(launch_sort(ctx->temp.p, tb, ctx->keys_in.as<unsigned>(), m->sorted_key.as<unsigned>(),
-                        ctx->vals_in.as<int>(), m->sorted_l.as<int>(), n, end_bit, s));
-    p.sorted_l = m->sorted_l.as<int>();
-    if (cols) {  // gather fused with the bucket starts
-        if ((rc = gather_buckets(ctx, m, kernel, p, n, nplanes))) return rc;
-        if (int rc2 = build_items(ctx, m, kernel)) return rc2;
-    } else {
-        HIP_TRY(launch_brick_start(m->sorted_key.as<unsigned>(), n, nplanes, bg.shift - 4,  // 4 = log2(BRICK2)
-                                   m->plane_start.as<int>(), s));
-        HIP_TRY(launch_gather_sorted(p, n, m->sorted_s.as<int>(), m->sorted_X.as<double>(), s));
-    }
-    return IBTK_LE_OK;
-}
-
 // ---------------------------------------------------------------------------
 // interp / spread
 // ---------------------------------------------------------------------------
@@ -968,33 +1028,11 @@ static int prepare(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, const ibtk_le
     if (m->npatch) return fail(IBTK_LE_ERR_ARG, "markers were binned for a level: use ibtk_le_level_interp/spread");
     if (!same_geom(m->geom, *geom)) return fail(IBTK_LE_ERR_ARG, "markers were binned for a different patch geometry");
     if (m->n > 0 && !X) return fail(IBTK_LE_ERR_ARG, "null X");
-    std::memset(&p, 0, sizeof(p));
-    p.bg = m->bg;
-    p.cg = m->cg;
-    p.S = m->S;
-    p.nseg = m->nseg;
-    p.items = m->items.as<SweepItem>();
-    p.nitems = m->nitems.as<int>();
-    p.item_bound = m->item_bound;
-    p.nbuckets_total = m->nbuckets_total;
-    p.sorted_a = m->sorted_a.as<unsigned>();
-    p.nsorted = m->n;
-    p.X = X;
-    p.indices = m->has_indices ? m->indices.as<int>() : nullptr;
-    p.Xshift = m->has_xshift ? m->xshift.as<double>() : nullptr;
-    p.sorted_l = m->sorted_l.as<int>();
-    p.sorted_s = m->sorted_s.as<int>();
-    p.sorted_X = m->sorted_X.as<double>();
-    p.sorted_X_ref = m->xcur_set ? m->xcur.as<double*>() : nullptr;
-    p.sorted_key = m->sorted_key.as<unsigned>();
-    p.plane_start = m->plane_start.as<int>();
-    p.err = ctx->err.as<int>();
-    p.sink = ctx->sink.as<double>();
-    p.tune = ctx->tune;
+    p = Params{};
+    handle_params(ctx, m, X, p);
     p.zmode = ctx->zmode;
     p.zlo = ctx->zlo;
     p.zhi = ctx->zhi;
-    p.K6 = ib6_K();
     p.h3 = geom->ndim == 3 ? (geom->dx[0] * geom->dx[1]) * geom->dx[2] : geom->dx[0] * geom->dx[1];
     return IBTK_LE_OK;
 }
@@ -1005,8 +1043,7 @@ static int prepare(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, const ibtk_le
 // (two host syncs; identity lists skip it).
 static int build_dedup(ibtk_le_ctx ctx, ibtk_le_markers m) {
     if (m->dedup_done) return IBTK_LE_OK;
-    m->dedup_done = true;
-    m->has_dups = false;
+    m->dedup_done = true;  // (has_dups is false: invalidate cleared both)
     if (!m->has_indices || m->n <= 1) return IBTK_LE_OK;
     const hipStream_t s = ctx->stream;
     int rc;
@@ -1110,7 +1147,7 @@ int ibtk_le::interp_impl(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, int cen
                          const double* const* q_dev, int q_depth, double* Q_dev, int Q_depth, const double* X_dev,
                          bool check_ghosts, const int* iper) {
     const ibtk_le_patch_geom* geom = static_cast<const ibtk_le_patch_geom*>(geomv);
-    Params p;
+    Params p{};
     if (int rc = prepare(ctx, m, kernel, geom, X_dev, p)) return rc;
     if (iper)
         for (int d = 0; d < 3; ++d) p.iper[d] = iper[d] ? 1 : 0;
@@ -1186,11 +1223,7 @@ static int build_candidates(ibtk_le_ctx ctx, ibtk_le_markers m, const Params& p)
     if ((rc = m->cand_idx.ensure(sizeof(int) * (size_t)m->n * 4))) return rc;
     HIP_TRY(hipMemsetAsync(m->cand_cnt.p, 0, sizeof(int) * (size_t)(items + 1), s));
     HIP_TRY(launch_cand(m->kernel, p, false, m->cand_cnt.as<int>(), nullptr, s));
-    size_t tb = 0;
-    HIP_TRY(launch_scan(nullptr, tb, m->cand_cnt.as<int>(), m->cand_off.as<int>(), items + 1, s));
-    if ((rc = ctx->temp.ensure(tb))) return rc;
-    tb = ctx->temp.cap;
-    HIP_TRY(launch_scan(ctx->temp.p, tb, m->cand_cnt.as<int>(), m->cand_off.as<int>(), items + 1, s));
+    if ((rc = scan_excl(ctx, m->cand_cnt.as<int>(), m->cand_off.as<int>(), items + 1))) return rc;
     HIP_TRY(launch_cand(m->kernel, p, true, m->cand_off.as<int>(), m->cand_idx.as<int>(), s));
     m->cand_valid = true;
     return IBTK_LE_OK;
@@ -1205,10 +1238,132 @@ static bool f_stream(ibtk_le_ctx ctx, ibtk_le_markers) {
     return ctx->tune.f_stream >= 0;
 }
 
+// The 3-D spread's candidate stream of m's binning (le_sweep.hip, launch_cand_stream):
+// built on the first spread after a binning, kept until the next; p.cs_* set.  A
+// closed-form kernel's components in a z frame shifted by -dz/2 (p.comp) need it split by
+// their anchor (cs_off_z): a stream built without the split is rebuilt with it, and one
+// built with it stands across a re-binning only if that moved no marker and changed no
+// shifted-z anchor (positions move within their cells).
+// A closed-form kernel's stream is always split by the shifted-z anchor, whichever
+// components a call spreads: the order of a column-anchor's candidates -- the order in
+// which they add into a point -- then depends on the binning alone, not on which
+// centerings were spread since it (advisor, round 5)
+static bool cand_split(int k) { return k == K_IB_4 || k == K_BSPLINE_4 || k == K_IB_6 || k == K_IB_4_W8; }
+// the stream stands as built: cand_stream launches nothing
+static bool cand_stream_built(ibtk_le_markers m, bool src) {
+    return m->cs_state == 1 && m->cs_pos.p && (m->cs_split || !cand_split(m->kernel)) && (!src || m->cs_has_src);
+}
+static int cand_stream(ibtk_le_ctx ctx, ibtk_le_markers m, Params& p) {
+    const long long ncl = (long long)m->nbuckets_total / NBAND;
+    const long long nclz = m->npatch ? m->nclz : (long long)m->cg.ncol * (m->cg.nz + 1);
+    const int k = m->kernel;
+    const bool split = cand_split(k);
+    const bool src = f_stream(ctx, m);  // the entries' marker rows beside their positions (Params::cs_src)
+    // A marker is a candidate of at most four columns (its own, one x- and one y-neighbour,
+    // the corner between them: a stencil never reaches both neighbours in a dim), so 4 n
+    // positions always hold the stream (16 bytes a marker; about 1.3 of the 4 are used by
+    // uniform IB_4 markers).  Offsets are 32-bit: a stream of 2^31 entries or more raises
+    // device flag 16 (k_cand_write checks its 64-bit length) instead of being refused here.
+    const long long cap = std::min(std::max(4LL * m->n, 1LL), (1LL << 31) - 1);
+    if (ncl + 1 >= (1LL << 31) || nclz + 1 >= (1LL << 31))
+        return fail(IBTK_LE_ERR_RANGE, "candidate stream too long");
+    p.cs_off = m->cs_off.as<int>();
+    p.cs_pos = m->cs_pos.as<int>();
+    p.cs_src = src ? m->cs_src.as<int>() : nullptr;
+    p.cs_total = (int)cap;
+    p.cs_off_z = m->cs_split ? m->cs_off_z.as<int>() : nullptr;
+    p.cs_rint = k == K_IB_4 ? 1 : 0;  // the IB_4 spread anchors by rint (spread_setup)
+    if (cand_stream_built(m, src)) return IBTK_LE_OK;
+    int rc;
+    // cs_cnt: ncl + 1 counts, then the stream's 64-bit length (8-byte aligned)
+    const size_t tot_at = (sizeof(int) * (size_t)(ncl + 1) + 7) / 8 * 8;
+    if ((rc = m->cs_cnt.ensure(tot_at + sizeof(unsigned long long)))) return rc;
+    if ((rc = m->cs_off.ensure(sizeof(int) * (size_t)(ncl + 1)))) return rc;
+    if ((rc = m->cs_pos.ensure(sizeof(int) * (size_t)cap))) return rc;
+    if (src && (rc = m->cs_src.ensure(sizeof(int) * (size_t)cap))) return rc;
+    if (split && (rc = m->cs_off_z.ensure(sizeof(int) * (size_t)(nclz + 1)))) return rc;
+    p.cs_off = m->cs_off.as<int>();
+    p.cs_pos = m->cs_pos.as<int>();
+    p.cs_src = src ? m->cs_src.as<int>() : nullptr;
+    p.cs_off_z = split ? m->cs_off_z.as<int>() : nullptr;
+    HIP_TRY(hipMemsetAsync(m->cs_cnt.as<int>() + ncl, 0, sizeof(int), ctx->stream));
+    size_t tb = 0;
+    HIP_TRY(launch_scan(nullptr, tb, m->cs_cnt.as<int>(), m->cs_off.as<int>(), (int)(ncl + 1), ctx->stream));
+    if ((rc = ctx->temp.ensure(tb))) return rc;
+    Params q = p;
+    // (a split stream stands across a re-binning that moved nothing only if no shifted-z
+    // anchor changed either: RebinBufs::zst[1])
+    // (nor does a stream without the source rows stand when they are wanted)
+    const bool keep = m->cs_state == 2 && (!split || (m->cs_split && m->zst.p)) && (!src || m->cs_has_src);
+    q.items_skip = keep ? m->cs_skip : nullptr;
+    q.cs_zflip = m->zst.p ? m->zst.as<int>() + 1 : nullptr;
+    q.cs_epoch = m->rb_epoch;
+    HIP_TRY(launch_cand_stream(q, (int)ncl, m->cs_cnt.as<int>(), m->cs_off.as<int>(), m->cs_pos.as<int>(),
+                               src ? m->cs_src.as<int>() : nullptr, ctx->temp.p, ctx->temp.cap,
+                               reinterpret_cast<unsigned long long*>(m->cs_cnt.as<char>() + tot_at), ctx->stream));
+    m->cs_state = 1;
+    m->cs_split = split;
+    m->cs_has_src = src;
+    return IBTK_LE_OK;
+}
+
+// One 3-D spread sweep of a prepared Params (its p.ncomp components): the candidate stream,
+// the diagnostic clocks and add counters around the launch, the timing events on a call's
+// first sweep.
+static int spread_sweep(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, Params& p, bool first) {
+    if (int rc = cand_stream(ctx, m, p)) return rc;
+    const size_t nst = (size_t)m->item_bound * p.ncomp * 8;
+    if (int rc = stamps_begin(ctx, nst, p)) return rc;
+    if (int rc = adds_begin(ctx, p, first)) return rc;
+    const bool t = ctx->timing && first;
+    HIP_TRY(launch_spread_sweep(kernel, p, ctx->stream, t ? ctx->ev0 : nullptr, t ? ctx->ev1 : nullptr));
+    if (int rc = adds_end(ctx, p)) return rc;
+    if (int rc = stamps_report(ctx, nst, p)) return rc;
+    if (t) ctx->ev_valid = true;
+    return IBTK_LE_OK;
+}
+
 static int spread_impl(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, int centering, int axis,
                        const ibtk_le_patch_geom* geom, double* const* q_dev, int q_depth, const double* Q_dev,
                        int Q_depth, const double* ds_dev, const double* X_dev, bool zero_ghosts = false,
-                       bool zero_first = false);
+                       bool zero_first = false) {
+    Params p{};
+    if (int rc = prepare(ctx, m, kernel, geom, X_dev, p)) return rc;
+    p.zero_ghosts = zero_ghosts ? 1 : 0;
+    p.zero_first = zero_first ? 1 : 0;
+    const int nc = ncomponents(geom, centering, q_depth, Q_depth);
+    if (nc < 0) return -nc;
+    if (m->n == 0) return IBTK_LE_OK;  // LEInteractor.cpp:2747
+    if (!Q_dev || !q_dev) return fail(IBTK_LE_ERR_ARG, "null Q or q");
+    if (set_device(ctx)) return IBTK_LE_ERR_DEVICE;
+    p.Qin = Q_dev;
+    p.ds = ds_dev;
+    p.Q_depth = Q_depth;
+    p.nsorted = m->n;
+    p.sorted_F = nullptr;
+    if (geom->ndim == 2 || !f_stream(ctx, m)) {  // (f_stream: the 3-D sweep reads Q at its rows)
+        if (int rc = ctx->fbuf.ensure(sizeof(double) * (size_t)m->n * (size_t)std::min(nc, MAXC))) return rc;
+        p.sorted_F = ctx->fbuf.as<double>();
+    }
+    if (geom->ndim == 2) {
+        if (int rc = build_candidates(ctx, m, p)) return rc;
+        p.cand_off = m->cand_off.as<int>();
+        p.cand_idx = m->cand_idx.as<int>();
+    }
+    ctx->ev_valid = false;
+    for (int first = 0; first < nc; first += MAXC) {
+        const int cnt = std::min(MAXC, nc - first);
+        if (int rc = make_comps(geom, centering, axis, q_dev, q_depth, Q_depth, first, cnt, p)) return rc;
+        if (geom->ndim == 3) {
+            if (int rc = spread_sweep(ctx, m, kernel, p, first == 0)) return rc;
+            continue;
+        }
+        const bool t = ctx->timing && first == 0;
+        HIP_TRY(launch_spread(kernel, p, ctx->stream, t ? ctx->ev0 : nullptr, t ? ctx->ev1 : nullptr));
+        if (t) ctx->ev_valid = true;
+    }
+    return IBTK_LE_OK;
+}
 
 extern "C" int ibtk_le_spread(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, int centering, int axis,
                               const ibtk_le_patch_geom* geom, double* const* q_dev, int q_depth, const double* Q_dev,
@@ -1237,7 +1392,7 @@ static int zero_comps(ibtk_le_ctx ctx, const ibtk_le_patch_geom* geom, int cente
     const int nc = ncomponents(geom, centering, q_depth, Q_depth);
     if (nc < 0) return -nc;
     if (set_device(ctx)) return IBTK_LE_ERR_DEVICE;
-    Params p;
+    Params p{};
     for (int first = 0; first < nc; first += MAXC) {
         const int cnt = std::min(MAXC, nc - first);
         if (int rc = make_comps(geom, centering, axis, q_dev, q_depth, Q_depth, first, cnt, p)) return rc;
@@ -1334,8 +1489,7 @@ static int user_call(ibtk_le_ctx ctx, bool spread, int centering, int axis, cons
     std::vector<int> lo((size_t)n * 3, 0), cnt((size_t)n * 3, 1);
     std::vector<double> w((size_t)n * 3 * S, 0.0);
     for (int c = 0; c < nc; ++c) {
-        Params p;
-        std::memset(&p, 0, sizeof(p));
+        Params p{};
         if ((rc = make_comps(geom, centering, axis, q_dev, q_depth, Q_depth, c, 1, p))) return rc;
         const CompDesc& cd = p.comp[0];
         if (spread) {
@@ -1432,122 +1586,6 @@ extern "C" int ibtk_le_user_spread(ibtk_le_ctx ctx, int centering, int axis, con
                      indices_dev, Xshift_dev, n);
 }
 
-// The 3-D spread's candidate stream of m's binning (le_sweep.hip, launch_cand_stream):
-// built on the first spread after a binning, kept until the next; p.cs_* set.  A
-// closed-form kernel's components in a z frame shifted by -dz/2 (p.comp) need it split by
-// their anchor (cs_off_z): a stream built without the split is rebuilt with it, and one
-// built with it stands across a re-binning only if that moved no marker and changed no
-// shifted-z anchor (positions move within their cells).
-// A closed-form kernel's stream is always split by the shifted-z anchor, whichever
-// components a call spreads: the order of a column-anchor's candidates -- the order in
-// which they add into a point -- then depends on the binning alone, not on which
-// centerings were spread since it (advisor, round 5)
-static bool cand_split(int k) { return k == K_IB_4 || k == K_BSPLINE_4 || k == K_IB_6 || k == K_IB_4_W8; }
-// the stream stands as built: cand_stream launches nothing
-static bool cand_stream_built(ibtk_le_markers m, bool src) {
-    return m->cs_state == 1 && m->cs_pos.p && (m->cs_split || !cand_split(m->kernel)) && (!src || m->cs_has_src);
-}
-static int cand_stream(ibtk_le_ctx ctx, ibtk_le_markers m, Params& p) {
-    const long long ncl = (long long)m->nbuckets_total / NBAND;
-    const long long nclz = m->npatch ? m->nclz : (long long)m->cg.ncol * (m->cg.nz + 1);
-    const int k = m->kernel;
-    const bool split = cand_split(k);
-    const bool src = f_stream(ctx, m);  // the entries' marker rows beside their positions (Params::cs_src)
-    // A marker is a candidate of at most four columns (its own, one x- and one y-neighbour,
-    // the corner between them: a stencil never reaches both neighbours in a dim), so 4 n
-    // positions always hold the stream (16 bytes a marker; about 1.3 of the 4 are used by
-    // uniform IB_4 markers).  Offsets are 32-bit: a stream of 2^31 entries or more raises
-    // device flag 16 (k_cand_write checks its 64-bit length) instead of being refused here.
-    const long long cap = std::min(std::max(4LL * m->n, 1LL), (1LL << 31) - 1);
-    if (ncl + 1 >= (1LL << 31) || nclz + 1 >= (1LL << 31))
-        return fail(IBTK_LE_ERR_RANGE, "candidate stream too long");
-    p.cs_off = m->cs_off.as<int>();
-    p.cs_pos = m->cs_pos.as<int>();
-    p.cs_src = src ? m->cs_src.as<int>() : nullptr;
-    p.cs_total = (int)cap;
-    p.cs_off_z = m->cs_split ? m->cs_off_z.as<int>() : nullptr;
-    p.cs_rint = k == K_IB_4 ? 1 : 0;  // the IB_4 spread anchors by rint (spread_setup)
-    if (cand_stream_built(m, src)) return IBTK_LE_OK;
-    int rc;
-    // cs_cnt: ncl + 1 counts, then the stream's 64-bit length (8-byte aligned)
-    const size_t tot_at = (sizeof(int) * (size_t)(ncl + 1) + 7) / 8 * 8;
-    if ((rc = m->cs_cnt.ensure(tot_at + sizeof(unsigned long long)))) return rc;
-    if ((rc = m->cs_off.ensure(sizeof(int) * (size_t)(ncl + 1)))) return rc;
-    if ((rc = m->cs_pos.ensure(sizeof(int) * (size_t)cap))) return rc;
-    if (src && (rc = m->cs_src.ensure(sizeof(int) * (size_t)cap))) return rc;
-    if (split && (rc = m->cs_off_z.ensure(sizeof(int) * (size_t)(nclz + 1)))) return rc;
-    p.cs_off = m->cs_off.as<int>();
-    p.cs_pos = m->cs_pos.as<int>();
-    p.cs_src = src ? m->cs_src.as<int>() : nullptr;
-    p.cs_off_z = split ? m->cs_off_z.as<int>() : nullptr;
-    HIP_TRY(hipMemsetAsync(m->cs_cnt.as<int>() + ncl, 0, sizeof(int), ctx->stream));
-    size_t tb = 0;
-    HIP_TRY(launch_scan(nullptr, tb, m->cs_cnt.as<int>(), m->cs_off.as<int>(), (int)(ncl + 1), ctx->stream));
-    if ((rc = ctx->temp.ensure(tb))) return rc;
-    Params q = p;
-    // (a split stream stands across a re-binning that moved nothing only if no shifted-z
-    // anchor changed either: RebinBufs::zst[1])
-    // (nor does a stream without the source rows stand when they are wanted)
-    const bool keep = m->cs_state == 2 && (!split || (m->cs_split && m->zst.p)) && (!src || m->cs_has_src);
-    q.items_skip = keep ? m->cs_skip : nullptr;
-    q.cs_zflip = m->zst.p ? m->zst.as<int>() + 1 : nullptr;
-    q.cs_epoch = m->rb_epoch;
-    HIP_TRY(launch_cand_stream(q, (int)ncl, m->cs_cnt.as<int>(), m->cs_off.as<int>(), m->cs_pos.as<int>(),
-                               src ? m->cs_src.as<int>() : nullptr, ctx->temp.p, ctx->temp.cap,
-                               reinterpret_cast<unsigned long long*>(m->cs_cnt.as<char>() + tot_at), ctx->stream));
-    m->cs_state = 1;
-    m->cs_split = split;
-    m->cs_has_src = src;
-    return IBTK_LE_OK;
-}
-
-static int spread_impl(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, int centering, int axis,
-                       const ibtk_le_patch_geom* geom, double* const* q_dev, int q_depth, const double* Q_dev,
-                       int Q_depth, const double* ds_dev, const double* X_dev, bool zero_ghosts, bool zero_first) {
-    Params p;
-    if (int rc = prepare(ctx, m, kernel, geom, X_dev, p)) return rc;
-    p.zero_ghosts = zero_ghosts ? 1 : 0;
-    p.zero_first = zero_first ? 1 : 0;
-    const int nc = ncomponents(geom, centering, q_depth, Q_depth);
-    if (nc < 0) return -nc;
-    if (m->n == 0) return IBTK_LE_OK;  // LEInteractor.cpp:2747
-    if (!Q_dev || !q_dev) return fail(IBTK_LE_ERR_ARG, "null Q or q");
-    if (set_device(ctx)) return IBTK_LE_ERR_DEVICE;
-    p.Qin = Q_dev;
-    p.ds = ds_dev;
-    p.Q_depth = Q_depth;
-    p.nsorted = m->n;
-    p.sorted_F = nullptr;
-    if (geom->ndim == 2 || !f_stream(ctx, m)) {  // (f_stream: the 3-D sweep reads Q at its rows)
-        if (int rc = ctx->fbuf.ensure(sizeof(double) * (size_t)m->n * (size_t)std::min(nc, MAXC))) return rc;
-        p.sorted_F = ctx->fbuf.as<double>();
-    }
-    if (geom->ndim == 2) {
-        if (int rc = build_candidates(ctx, m, p)) return rc;
-        p.cand_off = m->cand_off.as<int>();
-        p.cand_idx = m->cand_idx.as<int>();
-    }
-    ctx->ev_valid = false;
-    for (int first = 0; first < nc; first += MAXC) {
-        const int cnt = std::min(MAXC, nc - first);
-        if (int rc = make_comps(geom, centering, axis, q_dev, q_depth, Q_depth, first, cnt, p)) return rc;
-        const bool t = ctx->timing && first == 0;
-        if (geom->ndim == 3) {
-            if (int rc = cand_stream(ctx, m, p)) return rc;
-            const size_t nst = (size_t)m->item_bound * cnt * 8;
-            if (int rc = stamps_begin(ctx, nst, p)) return rc;
-            if (int rc = adds_begin(ctx, p, first == 0)) return rc;
-            HIP_TRY(launch_spread_sweep(kernel, p, ctx->stream, t ? ctx->ev0 : nullptr, t ? ctx->ev1 : nullptr));
-            if (int rc = adds_end(ctx, p)) return rc;
-            if (int rc = stamps_report(ctx, nst, p)) return rc;
-        } else {
-            HIP_TRY(launch_spread(kernel, p, ctx->stream, t ? ctx->ev0 : nullptr, t ? ctx->ev1 : nullptr));
-        }
-        if (t) ctx->ev_valid = true;
-    }
-    return IBTK_LE_OK;
-}
-
 // ---------------------------------------------------------------------------
 // a level of patches: LDataManager::spread / interp's patch loop
 // (LDataManager.cpp:625-660, 763-807) as one launch per sweep
@@ -1583,12 +1621,8 @@ extern "C" int ibtk_le_level_bin(ibtk_le_ctx ctx, ibtk_le_markers m, int npatch,
     const int n = entry_offsets[npatch];
     if (n > 0 && !X_dev) return fail(IBTK_LE_ERR_ARG, "null X");
     if (set_device(ctx)) return IBTK_LE_ERR_DEVICE;
-    const hipStream_t s = ctx->stream;
-    m->npatch = npatch;
-    m->geoms.assign(geoms, geoms + npatch);
-    std::vector<PatchDesc> prev;
-    prev.swap(m->pdh);
-    m->pdh.assign((size_t)npatch, PatchDesc{});
+    // the new patch table; the arrays of the last call stay with a table of the same length
+    std::vector<PatchDesc> pdh((size_t)npatch, PatchDesc{});
     long long nb = 0, nj = 0, nz = 0;
     BinGeom bg0{};
     for (int q = 0; q < npatch; ++q) {
@@ -1596,7 +1630,7 @@ extern "C" int ibtk_le_level_bin(ibtk_le_ctx ctx, ibtk_le_markers m, int npatch,
         ColGeom cg;
         if (int rc = make_col_geom(&geoms[q], kernel, bg, cg)) return rc;
         if (q == 0) bg0 = bg;
-        PatchDesc& P = m->pdh[q];
+        PatchDesc& P = pdh[q];
         std::memset(&P, 0, sizeof(P));
         P.cg = cg;
         P.bucket_base = (int)nb;
@@ -1607,17 +1641,19 @@ extern "C" int ibtk_le_level_bin(ibtk_le_ctx ctx, ibtk_le_markers m, int npatch,
             P.xlo[d] = geoms[q].x_lower[d];
             P.ilower[d] = geoms[q].ilower[d];
         }
-        if (prev.size() == (size_t)npatch) std::memcpy(P.comp, prev[q].comp, sizeof(P.comp));  // arrays of the last call
+        if (m->pdh.size() == (size_t)npatch) std::memcpy(P.comp, m->pdh[q].comp, sizeof(P.comp));
         nb += cg.nbuckets;
         nz += (long long)cg.ncol * (cg.nz + 1);
         nj += (long long)cg.ncol * P.nseg;
         if (nb + 1 >= (1LL << 31) || nj >= (1LL << 30)) return fail(IBTK_LE_ERR_RANGE, "level too large for 31-bit keys");
     }
+    m->npatch = npatch;
+    m->geoms.assign(geoms, geoms + npatch);
+    m->pdh.swap(pdh);
     m->nbuckets_total = (int)nb;
     m->nclz = nz;
     m->njobs = (int)nj;
     m->n = n;
-    m->kernel = kernel;
     m->ndim = 3;
     m->bg = bg0;
     m->cg = m->pdh[0].cg;
@@ -1626,13 +1662,10 @@ extern "C" int ibtk_le_level_bin(ibtk_le_ctx ctx, ibtk_le_markers m, int npatch,
     m->geom = geoms[0];
     m->has_indices = indices_dev != nullptr;
     m->has_xshift = Xshift_dev != nullptr;
-    m->cand_valid = false;
-    m->dedup_done = false;
-    m->qin_valid = false;
-    m->sel_cached = false;
-    m->has_dups = false;
     m->n_dev = nullptr;
     m->binned3 = true;
+    invalidate(m, BINNED);
+    m->kernel = -1;  // until the device phase is through
     int rc;
     if ((rc = upload_patches(ctx, m))) return rc;
     if (m->off_dev.size() != (size_t)(npatch + 1) ||
@@ -1640,51 +1673,11 @@ extern "C" int ibtk_le_level_bin(ibtk_le_ctx ctx, ibtk_le_markers m, int npatch,
         if ((rc = m->entry_off.ensure(sizeof(int) * (size_t)(npatch + 1)))) return rc;
         m->off_dev.assign(entry_offsets, entry_offsets + npatch + 1);
         HIP_TRY(hipMemcpyAsync(m->entry_off.p, m->off_dev.data(), sizeof(int) * (size_t)(npatch + 1),
-                               hipMemcpyHostToDevice, s));
+                               hipMemcpyHostToDevice, ctx->stream));
     }
-    if ((rc = m->plane_start.ensure(sizeof(int) * (size_t)(nb + 1)))) return rc;
-    if (n == 0) {
-        HIP_TRY(hipMemsetAsync(m->plane_start.p, 0, sizeof(int) * (size_t)(nb + 1), s));
-        return build_items(ctx, m, kernel);
-    }
-    if ((rc = m->sorted_key.ensure(sizeof(unsigned) * (size_t)n))) return rc;
-    if ((rc = m->sorted_l.ensure(sizeof(int) * (size_t)n))) return rc;
-    if ((rc = m->sorted_s.ensure(sizeof(int) * (size_t)n))) return rc;
-    if ((rc = m->sorted_X.ensure(sizeof(double) * (size_t)n * 3))) return rc;
-    if ((rc = ctx->keys_in.ensure(sizeof(unsigned) * (size_t)n))) return rc;
-    if ((rc = ctx->vals_in.ensure(sizeof(int) * (size_t)n))) return rc;
-    if (m->has_indices) {
-        if ((rc = m->indices.ensure(sizeof(int) * (size_t)n))) return rc;
-        HIP_TRY(hipMemcpyAsync(m->indices.p, indices_dev, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, s));
-    }
-    if (m->has_xshift) {
-        if ((rc = m->xshift.ensure(sizeof(double) * (size_t)n * 3))) return rc;
-        HIP_TRY(hipMemcpyAsync(m->xshift.p, Xshift_dev, sizeof(double) * (size_t)n * 3, hipMemcpyDeviceToDevice, s));
-    }
-    Params p;
-    std::memset(&p, 0, sizeof(p));
-    p.bg = bg0;
-    p.cg = m->cg;
-    p.pd = m->pd.as<PatchDesc>();
-    p.npatch = npatch;
-    p.entry_off = m->entry_off.as<int>();
-    p.nbuckets_total = (int)nb;
-    p.X = X_dev;
-    p.indices = m->has_indices ? m->indices.as<int>() : nullptr;
-    p.Xshift = m->has_xshift ? m->xshift.as<double>() : nullptr;
-    HIP_TRY(launch_bin_col(kernel, p, n, ctx->keys_in.as<unsigned>(), ctx->vals_in.as<int>(), s));
-    int end_bit = 1;
-    while ((1ULL << end_bit) <= (unsigned long long)nb) ++end_bit;
-    size_t tb = 0;
-    HIP_TRY(launch_sort(nullptr, tb, ctx->keys_in.as<unsigned>(), m->sorted_key.as<unsigned>(), ctx->vals_in.as<int>(),
-                        m->sorted_l.as<int>(), n, end_bit, s));
-    if ((rc = ctx->temp.ensure(tb))) return rc;
-    tb = ctx->temp.cap;
-    HIP_TRY(launch_sort(ctx->temp.p, tb, ctx->keys_in.as<unsigned>(), m->sorted_key.as<unsigned>(),
-                        ctx->vals_in.as<int>(), m->sorted_l.as<int>(), n, end_bit, s));
-    p.sorted_l = m->sorted_l.as<int>();
-    if ((rc = gather_buckets(ctx, m, kernel, p, n, (int)nb))) return rc;
-    return build_items(ctx, m, kernel);
+    if ((rc = bin_columns(ctx, m, kernel, X_dev, indices_dev, Xshift_dev))) return rc;
+    m->kernel = kernel;
+    return IBTK_LE_OK;
 }
 
 // Params of a level call: the patch table with the component arrays of this
@@ -1710,58 +1703,25 @@ static int level_params(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, int cent
                 return fail(IBTK_LE_ERR_GHOST_WIDTH, "LEInteractor::interpolate(): insufficient ghost cells in patch %d",
                             q);
         }
-        Params t;
-        std::memset(&t, 0, sizeof(t));
+        Params t{};
         if (int rc = make_comps(&g, centering, axis, q_dev + (size_t)q * per, q_depth, Q_depth, 0, nc, t)) return rc;
         std::memcpy(m->pdh[q].comp, t.comp, sizeof(t.comp));
         if (q == 0) std::memcpy(p.comp, t.comp, sizeof(t.comp));
     }
-    p.tune = ctx->tune;
     if (set_device(ctx)) return IBTK_LE_ERR_DEVICE;
-    if (int rc = upload_patches(ctx, m)) return rc;
+    if (int rc = upload_patches(ctx, m)) return rc;  // (before handle_params: the upload may move m->pd)
+    handle_params(ctx, m, X, p);
     p.ncomp = nc;
-    p.bg = m->bg;
-    p.cg = m->cg;
-    p.S = m->S;
-    p.nseg = m->nseg;
-    p.pd = m->pd.as<PatchDesc>();
-    p.npatch = m->npatch;
-    p.entry_off = m->entry_off.as<int>();
-    p.nbuckets_total = m->nbuckets_total;
     p.njobs = m->njobs;
-    p.items = m->items.as<SweepItem>();
-    p.nitems = m->nitems.as<int>();
-    p.item_bound = m->item_bound;
-    p.nsorted = m->n;
-    p.X = X;
-    p.indices = m->has_indices ? m->indices.as<int>() : nullptr;
-    p.Xshift = m->has_xshift ? m->xshift.as<double>() : nullptr;
-    p.sorted_l = m->sorted_l.as<int>();
-    p.sorted_s = m->sorted_s.as<int>();
-    p.sorted_X = m->sorted_X.as<double>();
-    p.sorted_X_ref = m->xcur_set ? m->xcur.as<double*>() : nullptr;
-    p.sorted_key = m->sorted_key.as<unsigned>();
-    p.plane_start = m->plane_start.as<int>();
-    p.err = ctx->err.as<int>();
-    p.sink = ctx->sink.as<double>();
-    p.K6 = ib6_K();
     p.h3 = (m->geoms[0].dx[0] * m->geoms[0].dx[1]) * m->geoms[0].dx[2];
     p.Q_depth = Q_depth;
     return IBTK_LE_OK;
 }
 
-extern "C" int ibtk_le_level_interp(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, int centering, int axis,
-                                    const double* const* q_dev, int q_depth, double* Q_dev, int Q_depth,
-                                    const double* X_dev) {
-    Params p;
-    std::memset(&p, 0, sizeof(p));
-    int nc = 0;
-    if (int rc = level_params(ctx, m, kernel, centering, axis, const_cast<double* const*>(q_dev), q_depth, Q_depth,
-                              X_dev, true, p, nc))
-        return rc;
-    if (m->n == 0) return IBTK_LE_OK;
-    if (!Q_dev) return fail(IBTK_LE_ERR_ARG, "null Q");
-    if (m->qin_valid) {  // the interior entries only (each names its marker once)
+// One level interp sweep of a prepared Params into Q_dev: written from the selected
+// interior entries (each names its marker once), else from each marker's last entry.
+static int level_interp_sweep(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, Params& p, double* Q_dev) {
+    if (m->qin_valid) {
         p.qdst = m->qin.as<int>();
     } else {
         if (int rc = build_dedup(ctx, m)) return rc;
@@ -1773,6 +1733,19 @@ extern "C" int ibtk_le_level_interp(ibtk_le_ctx ctx, ibtk_le_markers m, int kern
     HIP_TRY(launch_interp_sweep(kernel, p, m->n, ctx->stream, t ? ctx->ev0 : nullptr, t ? ctx->ev1 : nullptr));
     if (t) ctx->ev_valid = true;
     return IBTK_LE_OK;
+}
+
+extern "C" int ibtk_le_level_interp(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, int centering, int axis,
+                                    const double* const* q_dev, int q_depth, double* Q_dev, int Q_depth,
+                                    const double* X_dev) {
+    Params p{};
+    int nc = 0;
+    if (int rc = level_params(ctx, m, kernel, centering, axis, const_cast<double* const*>(q_dev), q_depth, Q_depth,
+                              X_dev, true, p, nc))
+        return rc;
+    if (m->n == 0) return IBTK_LE_OK;
+    if (!Q_dev) return fail(IBTK_LE_ERR_ARG, "null Q");
+    return level_interp_sweep(ctx, m, kernel, p, Q_dev);
 }
 
 // LDataManager::interp's patch loop takes each patch's interior list
@@ -1788,14 +1761,15 @@ extern "C" int ibtk_le_level_interp(ibtk_le_ctx ctx, ibtk_le_markers m, int kern
 // a new list was allocated at the old address)
 extern "C" int ibtk_le_level_select_interior_reset(ibtk_le_markers m) {
     if (!m) return fail(IBTK_LE_ERR_ARG, "select_interior_reset: null markers");
-    m->sel_cached = false;
+    invalidate(m, RESELECT);
     return IBTK_LE_OK;
 }
 
 extern "C" int ibtk_le_level_select_interior(ibtk_le_ctx ctx, ibtk_le_markers m, int n_markers,
                                              const int* interior_offsets, const int* interior_indices_dev) {
     if (!ctx || !m || !interior_offsets) return fail(IBTK_LE_ERR_ARG, "select_interior: null argument");
-    if (m->npatch <= 0) return fail(IBTK_LE_ERR_ARG, "select_interior: not a level binning (ibtk_le_level_bin)");
+    if (m->npatch <= 0 || m->kernel < 0)
+        return fail(IBTK_LE_ERR_ARG, "select_interior: not a level binning (ibtk_le_level_bin)");
     const int np = m->npatch;
     if (interior_offsets[0] != 0) return fail(IBTK_LE_ERR_ARG, "select_interior: offsets[0] must be 0");
     for (int q = 0; q < np; ++q)
@@ -1867,8 +1841,7 @@ extern "C" int ibtk_le_level_select_interior(ibtk_le_ctx ctx, ibtk_le_markers m,
 static int level_spread_impl(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, int centering, int axis,
                              double* const* q_dev, int q_depth, const double* Q_dev, int Q_depth, const double* X_dev,
                              bool zero_first) {
-    Params p;
-    std::memset(&p, 0, sizeof(p));
+    Params p{};
     int nc = 0;
     if (int rc = level_params(ctx, m, kernel, centering, axis, q_dev, q_depth, Q_depth, X_dev, false, p, nc))
         return rc;
@@ -1882,17 +1855,8 @@ static int level_spread_impl(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, int
         if (int rc = ctx->fbuf.ensure(sizeof(double) * (size_t)m->n * (size_t)nc)) return rc;
         p.sorted_F = ctx->fbuf.as<double>();
     }
-    if (int rc = cand_stream(ctx, m, p)) return rc;
-    const bool t = ctx->timing;
     ctx->ev_valid = false;
-    const size_t nst = (size_t)m->item_bound * nc * 8;
-    if (int rc = stamps_begin(ctx, nst, p)) return rc;
-    if (int rc = adds_begin(ctx, p, true)) return rc;
-    HIP_TRY(launch_spread_sweep(kernel, p, ctx->stream, t ? ctx->ev0 : nullptr, t ? ctx->ev1 : nullptr));
-    if (int rc = adds_end(ctx, p)) return rc;
-    if (int rc = stamps_report(ctx, nst, p)) return rc;
-    if (t) ctx->ev_valid = true;
-    return IBTK_LE_OK;
+    return spread_sweep(ctx, m, kernel, p, true);
 }
 
 extern "C" int ibtk_le_level_spread(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, int centering, int axis,
@@ -2049,15 +2013,13 @@ extern "C" int ibtk_le_level_fill_interp(ibtk_le_ctx ctx, ibtk_le_markers m, int
         const KernelInfo ki = kKernelInfo[kernel < 0 || kernel >= K_COUNT ? 0 : kernel];
         if (t.n[0] < COLX + ki.HI - ki.LO || t.n[1] < COLY + ki.HI - ki.LO) return unfused();
     }
-    Params p;
-    std::memset(&p, 0, sizeof(p));
+    Params p{};
     int nc = 0;
     if (int rc = level_params(ctx, m, kernel, centering, axis, q_dev, q_depth, Q_depth, X_dev, true, p, nc)) return rc;
     if (m->n == 0) return IBTK_LE_OK;
     if (!Q_dev) return fail(IBTK_LE_ERR_ARG, "null Q");
     // each component's window: its arrays' lowest start to highest end, below 2 GB
     // (buffer offsets are 32-bit and OFF_NONE is 2^31)
-    const int per = t.side ? 3 : 1;
     uintptr_t wlo[MAXC], whi[MAXC];
     for (int c = 0; c < nc; ++c) {
         wlo[c] = UINTPTR_MAX;
@@ -2071,7 +2033,6 @@ extern "C" int ibtk_le_level_fill_interp(ibtk_le_ctx ctx, ibtk_le_markers m, int
         }
         if (whi[c] - wlo[c] >= (uintptr_t(1) << 31)) return unfused();
     }
-    (void)per;
     // the record per component and patch (le_sweep.hip LVL_REC): the 27 suppliers, the window
     constexpr int REC = 32;
     std::vector<int2> tab((size_t)nc * np * REC, make_int2(0, 0));
@@ -2097,18 +2058,7 @@ extern "C" int ibtk_le_level_fill_interp(ibtk_le_ctx ctx, ibtk_le_markers m, int
     }
     p.lvl_nbr = m->lvl_nbr.as<int2>();
     for (int d = 0; d < 3; ++d) p.lvl_n[d] = t.n[d];
-    if (m->qin_valid) {
-        p.qdst = m->qin.as<int>();
-    } else {
-        if (int rc = build_dedup(ctx, m)) return rc;
-        p.qdst = m->has_dups ? m->qdst.as<int>() : nullptr;
-    }
-    p.Qout = Q_dev;
-    const bool tm = ctx->timing;
-    ctx->ev_valid = false;
-    HIP_TRY(launch_interp_sweep(kernel, p, m->n, ctx->stream, tm ? ctx->ev0 : nullptr, tm ? ctx->ev1 : nullptr));
-    if (tm) ctx->ev_valid = true;
-    return IBTK_LE_OK;
+    return level_interp_sweep(ctx, m, kernel, p, Q_dev);
 }
 
 extern "C" int ibtk_le_level_zero(ibtk_le_ctx ctx, int npatch, const ibtk_le_patch_geom* geoms, int centering,
@@ -2488,11 +2438,8 @@ extern "C" int ibtk_le_imp_spread(ibtk_le_ctx ctx, ibtk_le_markers m, const ibtk
     HIP_TRY(launch_imp_keys(P, s));
     int end_bit = 1;
     while ((1ULL << end_bit) <= (unsigned long long)ncells) ++end_bit;
-    size_t tb = 0;
-    HIP_TRY(launch_sort(nullptr, tb, P.keys, ctx->imp_skey.as<unsigned>(), P.vals, ctx->imp_sval.as<int>(), n, end_bit, s));
-    if ((rc = ctx->temp.ensure(tb))) return rc;
-    tb = ctx->temp.cap;
-    HIP_TRY(launch_sort(ctx->temp.p, tb, P.keys, ctx->imp_skey.as<unsigned>(), P.vals, ctx->imp_sval.as<int>(), n, end_bit, s));
+    if ((rc = sort_pairs(ctx, P.keys, ctx->imp_skey.as<unsigned>(), P.vals, ctx->imp_sval.as<int>(), n, end_bit)))
+        return rc;
     HIP_TRY(launch_key_offsets(ctx->imp_skey.as<unsigned>(), n, 1u, P.ncells, ctx->imp_start.as<int>(), s));
     HIP_TRY(launch_imp_spread(P, s));
     return IBTK_LE_OK;
@@ -2689,11 +2636,7 @@ static int compact_by_flags(ibtk_le_ctx ctx, int ndim, int n, const int* flag, c
     int rc;
     if ((rc = ctx->lst_flag.ensure(sizeof(int) * (size_t)n))) return rc;
     int* pos = ctx->lst_flag.as<int>();
-    size_t tb = 0;
-    HIP_TRY(launch_scan(nullptr, tb, flag, pos, n, s));
-    if ((rc = ctx->temp.ensure(tb))) return rc;
-    tb = ctx->temp.cap;
-    HIP_TRY(launch_scan(ctx->temp.p, tb, flag, pos, n, s));
+    if ((rc = scan_excl(ctx, flag, pos, n))) return rc;
     int last[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(&last[0], pos + n - 1, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(&last[1], flag + n - 1, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -2749,21 +2692,16 @@ static int sort_cell_lag(ibtk_le_ctx ctx, const unsigned* cell_keys, const int* 
     unsigned* k0 = kbuf.as<unsigned>();
     unsigned* k1 = k0 + n;
     int* v0 = vbuf.as<int>();
-    size_t tb = 0;
-    HIP_TRY(launch_sort(nullptr, tb, k0, k1, v0, perm, n, 32, s));
-    if ((rc = ctx->temp.ensure(tb))) return rc;
-    tb = ctx->temp.cap;
     HIP_TRY(launch_iota(v0, n, s));
     if (lag) {  // pass 1 (entries are generated in marker order: the marker index needs no pass)
         HIP_TRY(launch_perm_keys(0, nullptr, idx, lag, nullptr, n, k0, s));
-        HIP_TRY(launch_sort(ctx->temp.p, tb, k0, k1, v0, perm, n, 32, s));
+        if ((rc = sort_pairs(ctx, k0, k1, v0, perm, n, 32))) return rc;
         HIP_TRY(hipMemcpyAsync(v0, perm, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, s));
     }
     HIP_TRY(launch_perm_keys(1, v0, nullptr, nullptr, cell_keys, n, k0, s));
     int end_bit = 1;
     while (end_bit < 32 && (1ull << end_bit) <= key_end) ++end_bit;
-    HIP_TRY(launch_sort(ctx->temp.p, tb, k0, k1, v0, perm, n, end_bit, s));
-    return IBTK_LE_OK;
+    return sort_pairs(ctx, k0, k1, v0, perm, n, end_bit);
 }
 
 // The index lists of one patch (LIndexSetData::cacheLocalIndices, LIndexSetData.cpp:
@@ -2807,11 +2745,7 @@ static int index_list_impl(ibtk_le_ctx ctx, const ibtk_le_patch_geom* geom, cons
     if ((rc = ctx->offsets.ensure(sizeof(int) * (size_t)n_markers))) return rc;
     const hipStream_t s = ctx->stream;
     HIP_TRY(launch_image_count(d, X_dev, n_markers, ctx->counts.as<int>(), s));
-    size_t tb = 0;
-    HIP_TRY(launch_scan(nullptr, tb, ctx->counts.as<int>(), ctx->offsets.as<int>(), n_markers, s));
-    if ((rc = ctx->temp.ensure(tb))) return rc;
-    tb = ctx->temp.cap;
-    HIP_TRY(launch_scan(ctx->temp.p, tb, ctx->counts.as<int>(), ctx->offsets.as<int>(), n_markers, s));
+    if ((rc = scan_excl(ctx, ctx->counts.as<int>(), ctx->offsets.as<int>(), n_markers))) return rc;
     int last[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(&last[0], ctx->offsets.as<int>() + n_markers - 1, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(&last[1], ctx->counts.as<int>() + n_markers - 1, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -2899,11 +2833,7 @@ extern "C" int ibtk_le_node_distribution(ibtk_le_ctx ctx, const ibtk_le_patch_ge
     int* flag = ctx->lst_idx.as<int>();
     int* pos = flag + n;
     HIP_TRY(launch_unique_flags(skeys, ctx->lst_perm.as<int>(), lag_dev, n, flag, s));
-    size_t tb = 0;
-    HIP_TRY(launch_scan(nullptr, tb, flag, pos, n, s));
-    if ((rc = ctx->temp.ensure(tb))) return rc;
-    tb = ctx->temp.cap;
-    HIP_TRY(launch_scan(ctx->temp.p, tb, flag, pos, n, s));
+    if ((rc = scan_excl(ctx, flag, pos, n))) return rc;
     HIP_TRY(hipMemsetAsync(ctx->counts.p, 0, 2 * sizeof(int), s));
     HIP_TRY(launch_compact(ctx->lst_perm.as<int>(), flag, pos, skeys, (unsigned)ncell, (unsigned)(ncell + gcells), n,
                            order_dev, ctx->counts.as<int>(), s));
@@ -2912,18 +2842,6 @@ extern "C" int ibtk_le_node_distribution(ibtk_le_ctx ctx, const ibtk_le_patch_ge
     HIP_TRY(hipStreamSynchronize(s));
     *n_local = cnt[0];
     *n_nonlocal = cnt[1];
-    return IBTK_LE_OK;
-}
-
-// Stable sort of (keys, vals) on the context stream: out_keys/out_vals may be
-// scratch of the caller; uses ctx->temp.
-static int sort_pairs(ibtk_le_ctx ctx, const unsigned* kin, unsigned* kout, const int* vin, int* vout, int n,
-                      int end_bit) {
-    size_t tb = 0;
-    HIP_TRY(launch_sort(nullptr, tb, kin, kout, vin, vout, n, end_bit, ctx->stream));
-    if (int rc = ctx->temp.ensure(tb)) return rc;
-    tb = ctx->temp.cap;
-    HIP_TRY(launch_sort(ctx->temp.p, tb, kin, kout, vin, vout, n, end_bit, ctx->stream));
     return IBTK_LE_OK;
 }
 
@@ -3275,11 +3193,7 @@ extern "C" int ibtk_le_local_numbering(ibtk_le_ctx ctx, const ibtk_le_patch_geom
                              s));
     int end_bit = 1;
     while ((1ull << end_bit) <= ncells) ++end_bit;
-    size_t tb = 0;
-    HIP_TRY(launch_sort(nullptr, tb, kin, kout, ctx->vals_in.as<int>(), order_dev, n_markers, end_bit, s));
-    if ((rc = ctx->temp.ensure(tb))) return rc;
-    tb = ctx->temp.cap;
-    HIP_TRY(launch_sort(ctx->temp.p, tb, kin, kout, ctx->vals_in.as<int>(), order_dev, n_markers, end_bit, s));
+    if ((rc = sort_pairs(ctx, kin, kout, ctx->vals_in.as<int>(), order_dev, n_markers, end_bit))) return rc;
     if (n_interior) {
         HIP_TRY(hipMemcpyAsync(n_interior, ctx->counts.p, sizeof(int), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -3290,7 +3204,7 @@ extern "C" int ibtk_le_local_numbering(ibtk_le_ctx ctx, const ibtk_le_patch_geom
 extern "C" int ibtk_le_mark_stencils(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, int centering, int axis,
                                      const ibtk_le_patch_geom* geom, unsigned char* const* masks_dev, int q_depth,
                                      const double* X_dev) {
-    Params p;
+    Params p{};
     if (int rc = prepare(ctx, m, kernel, geom, X_dev, p)) return rc;
     const int nc = ncomponents(geom, centering, q_depth, centering == IBTK_LE_SIDE || centering == IBTK_LE_EDGE
                                                             ? geom->ndim

@@ -137,63 +137,61 @@ struct PatchDesc {
 };
 
 struct Params {
-    BinGeom bg;
-    ColGeom cg;                // 3-D column binning
-    const unsigned* sorted_a;  // sorted position -> packed key cell (x | y << 16), relative to cg.org
-    int S, nseg;               // sweep segment length (planes) and segments per column
-    const PatchDesc* pd;       // 3-D level: per-patch descriptors (nullptr: one patch, cg/comp/bg above)
-    int npatch;
-    const int* entry_off;      // level: list entries of patch q are [entry_off[q], entry_off[q+1])
-    int nbuckets_total;        // buckets of every patch (entries keyed >= it are outside)
-    int njobs;                 // (segment, column) pairs of every patch
-    int strip;                 // item order: column rows per strip (job_column)
-    int ncut, cut[4];          // item table: extra cuts at these relative planes (the plane window's edges)
-    int zmode, zlo, zhi;       // plane window (ibtk_le_ctx_set_plane_window): 0 every item, 1 the items
+    BinGeom bg{};
+    ColGeom cg{};              // 3-D column binning
+    int S = 0, nseg = 0;       // sweep segment length (planes) and segments per column
+    const PatchDesc* pd = nullptr;  // 3-D level: per-patch descriptors (nullptr: one patch, cg/comp/bg above)
+    int npatch = 0;
+    const int* entry_off = nullptr;  // level: list entries of patch q are [entry_off[q], entry_off[q+1])
+    int nbuckets_total = 0;    // buckets of every patch (entries keyed >= it are outside)
+    int njobs = 0;             // (segment, column) pairs of every patch
+    int strip = 0;             // item order: column rows per strip (job_column)
+    int ncut = 0, cut[4] = {0, 0, 0, 0};  // item table: extra cuts at these relative planes (the plane window's edges)
+    int zmode = 0, zlo = 0, zhi = 0;  // plane window (ibtk_le_ctx_set_plane_window): 0 every item, 1 the items
                                // whose planes lie in [zlo, zhi], 2 the others
-    const SweepItem* items;    // 3-D sweep item table (k_item_write)
-    const int* items_skip;     // k_item_counts / k_item_write: nothing to do when *items_skip == 0 (a
+    const SweepItem* items = nullptr;  // 3-D sweep item table (k_item_write)
+    const int* items_skip = nullptr;  // k_item_counts / k_item_write: nothing to do when *items_skip == 0 (a
                                // re-binning that moved nothing leaves the bucket starts, so the table, as they were)
-    const int* nitems;         // device: its length, then the count of heavy items heading it
-    int item_bound;            // host: an upper bound of the length (the launch grid)
+    const int* nitems = nullptr;  // device: its length, then the count of heavy items heading it
+    int item_bound = 0;        // host: an upper bound of the length (the launch grid)
     SweepTune tune;
-    int ncomp;
-    CompDesc comp[MAXC];
-    int Q_depth;
-    double h3;                 // dx0*dx1[*dx2], associated as the Fortran does
-    double K6;                 // IB_6 parameter K
-    const double* X;           // AoS positions
-    const int* indices;        // list entry -> marker (nullptr: identity)
-    const double* Xshift;      // list entry -> shift[NDIM] (nullptr: zero)
-    const int* sorted_l;       // sorted position -> list entry
-    const int* sorted_s;       // sorted position -> marker index
-    const double* sorted_X;    // sorted position -> X(s) + Xshift(l) [NDIM]
-    const double* const* sorted_X_ref;  // 3-D: device cell naming the current sorted positions (or null: sorted_X)
-    const unsigned* sorted_key;
-    const int* plane_start;    // nbricks*B + 1 offsets into the sorted list: bucket = key >> (shift - log2 B)
+    int ncomp = 0;
+    CompDesc comp[MAXC] = {};
+    int Q_depth = 0;
+    double h3 = 0.0;           // dx0*dx1[*dx2], associated as the Fortran does
+    double K6 = 0.0;           // IB_6 parameter K
+    const double* X = nullptr;  // AoS positions
+    const int* indices = nullptr;  // list entry -> marker (nullptr: identity)
+    const double* Xshift = nullptr;  // list entry -> shift[NDIM] (nullptr: zero)
+    const int* sorted_l = nullptr;  // sorted position -> list entry
+    const int* sorted_s = nullptr;  // sorted position -> marker index
+    const double* sorted_X = nullptr;  // sorted position -> X(s) + Xshift(l) [NDIM]
+    const double* const* sorted_X_ref = nullptr;  // 3-D: device cell naming the current sorted positions (or null: sorted_X)
+    const unsigned* sorted_key = nullptr;
+    const int* plane_start = nullptr;  // nbricks*B + 1 offsets into the sorted list: bucket = key >> (shift - log2 B)
                                // (brick b's entries are [plane_start[b*B], plane_start[(b+1)*B]))
-    const int* cand_off;       // spread: (super-brick, class) candidate lists: offsets, items*NCLS + 1
-    const int* cand_idx;       // spread: candidate sorted positions, canonical order per super-brick
-    const int* cs_off;         // 3-D spread: candidate stream offsets per column-anchor (launch_cand_stream)
-    const int* cs_pos;         // 3-D spread: the candidate stream (sorted positions)
+    const int* cand_off = nullptr;  // spread: (super-brick, class) candidate lists: offsets, items*NCLS + 1
+    const int* cand_idx = nullptr;  // spread: candidate sorted positions, canonical order per super-brick
+    const int* cs_off = nullptr;  // 3-D spread: candidate stream offsets per column-anchor (launch_cand_stream)
+    const int* cs_pos = nullptr;  // 3-D spread: the candidate stream (sorted positions)
     const int* cs_src = nullptr;  // beside cs_pos: the marker row of each entry, sorted_s[cs_pos[j]] (k_cand_write);
                                // the sweep then reads F at its row.  nullptr: sorted_F (launch_gather_F)
-    int cs_total;              // its length
-    const int* cs_off_z;       // closed-form kernels: the stream's boundaries per anchor of the frame
+    int cs_total = 0;          // its length
+    const int* cs_off_z = nullptr;  // closed-form kernels: the stream's boundaries per anchor of the frame
                                // shifted by -dz/2 in z (side-z, node, x/y-edge components; k_cand_write)
-    int cs_rint;               // the spread's stencils anchor by rint (IB_4), not NINT
-    const int* cs_zflip;       // with cs_off_z and items_skip: == cs_epoch when a shifted-z anchor changed
-    int cs_epoch;              //     in the last re-binning (RebinBufs::zst, epoch)
-    const int* nentries_dev;   // device copy of the list length
-    const double* Qin;         // spread: marker values
-    const double* sorted_F;    // spread: Qin gathered in sorted order, [comp][sorted position]
-    const double* ds;          // spread: per-marker weight (nullptr: none); sorted_F = Qin * ds
-    int nsorted;               // list length
-    double* Qout;              // interp: marker values
-    const int* qdst;           // interp: per sorted entry, the marker whose Q it writes, or -1 when a later
+    int cs_rint = 0;           // the spread's stencils anchor by rint (IB_4), not NINT
+    const int* cs_zflip = nullptr;  // with cs_off_z and items_skip: == cs_epoch when a shifted-z anchor changed
+    int cs_epoch = 0;          //     in the last re-binning (RebinBufs::zst, epoch)
+    const double* Qin = nullptr;  // spread: marker values
+    const double* sorted_F = nullptr;  // spread: Qin gathered in sorted order, [comp][sorted position]
+    const double* ds = nullptr;  // spread: per-marker weight (nullptr: none); sorted_F = Qin * ds
+    int nsorted = 0;           // list length
+    double* Qout = nullptr;    // interp: marker values
+    const int* qdst = nullptr;  // interp: per sorted entry, the marker whose Q it writes, or -1 when a later
                                // list entry of the same marker writes it (the Fortran's sequential l-loop
                                // overwrites: the last occurrence wins); nullptr = sorted_s (no duplicates)
-    int* err;                  // device error word (0 = fine)
-    double* sink;              // 64 doubles: the store target of masked-off lanes (branch-free stores)
+    int* err = nullptr;        // device error word (0 = fine)
+    double* sink = nullptr;    // 64 doubles: the store target of masked-off lanes (branch-free stores)
     const int* n_dev = nullptr;  // bin: the list's length on the device (entries beyond it binned outside)
     unsigned long long* stamps = nullptr;  // diagnostic phase clocks (nullptr: off)
     unsigned long long* nadd = nullptr;    // spread: [ds_add_f64 wave-instructions, lane adds] issued (nullptr: not counted)

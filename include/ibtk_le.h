@@ -149,7 +149,10 @@ int ibtk_le_ctx_synchronize(ibtk_le_ctx ctx);
  * device by the stencil anchor cell of X(s)+Xshift (stable radix sort; 3-D:
  * buckets of (anchor plane, 32x16-cell column, reach band); 2-D: bricks of 16^2
  * cells).  The handle keeps device copies of the sorted list, and a pointer to its
- * context: destroy a context's markers before the context. */
+ * context: destroy a context's markers before the context.
+ * A binning refused before any device allocation or launch (argument, geometry and range
+ * checks) leaves the handle exactly as it was; one that fails later (NOMEM, a HIP error)
+ * leaves it unbinned: interp, spread and rebin return IBTK_LE_ERR_ARG until the next binning. */
 int ibtk_le_markers_create(ibtk_le_ctx ctx, ibtk_le_markers* out);
 int ibtk_le_markers_destroy(ibtk_le_markers m);
 int ibtk_le_markers_bin(ibtk_le_ctx ctx, ibtk_le_markers m, const ibtk_le_patch_geom* geom, int kernel,
@@ -250,7 +253,10 @@ int ibtk_le_spread_ds(ibtk_le_ctx ctx, ibtk_le_markers m, int kernel, int center
  * spread in each patch's own fixed order).
  * Limit: a level interp / spread / zero_spread / fill_interp takes at most 4
  * components (CELL / NODE: q_depth <= 4); more returns IBTK_LE_ERR_ARG ("level calls
- * take at most 4 components") and writes nothing. */
+ * take at most 4 components") and writes nothing.
+ * ibtk_le_level_bin fails as ibtk_le_markers_bin does: refused before any device allocation
+ * or launch (argument, geometry and range checks of every patch), the handle is exactly as it
+ * was; failing later (NOMEM, a HIP error), it is unbinned and later calls return IBTK_LE_ERR_ARG. */
 int ibtk_le_level_bin(ibtk_le_ctx ctx, ibtk_le_markers m, int npatch, const ibtk_le_patch_geom* geoms, int kernel,
                       const double* X_dev, const int* entry_offsets, const int* indices_dev,
                       const double* Xshift_dev);

@@ -4,8 +4,8 @@ IBAMR keeps one handle per patch level for a whole run and bins it again after e
 another list length, other boxes, other lists, and one Context serves several handles.  The
 handle carries some twenty pieces of derived state that outlive a binning (the candidate
 stream and its flags, the re-binning's counts and parities, the item table's signature, the
-duplicate map, the interior selection, host mirrors of device tables), each invalidated by
-hand at three entry points.  The property held here: after any sequence of calls, every array
+duplicate map, the interior selection, host mirrors of device tables), invalidated by hand
+(le_abi.cpp: invalidate() and build_items).  The property held here: after any sequence of calls, every array
 an interp, spread, zero_spread, zero_ghosts_spread or fill_interp writes, Markers.order() and
 Markers.count() are bit for bit (torch.equal) what a fresh Context and a fresh handle give
 that saw only the last binning and the same final call -- ibtk_le.h's own promise that a
@@ -540,3 +540,42 @@ def test_handles_share_a_context(le, env, levels):
     want = level_fresh(le, L, "X_moved", F3)
     same(level_calls(le, L, lvl, "X_moved", F3), want, "level re-binned after the others")
     level_oracle_check(L, "X_moved", 21, want)
+
+
+def test_refused_level_bin_leaves_the_handle(le, env, levels):
+    """12. A level binning refused before its device phase leaves the handle as it was
+    (ibtk_le.h, ibtk_le_level_bin).  LA is binned, interpolated and spread; the same handle is
+    then offered two patches, LA's first and one of 70 000 x 4 x 4 cells: its 70 007 x 11
+    array plane passes the geometry check, and its key cells in x pass the 65 535 that the
+    packed 16-bit key cells hold, so the call fails with RANGE (7) at the second patch, after
+    the first was laid out.  The level object of the first binning then gives its bits again."""
+    from ibamr_amd._lib import IBTKLEError
+    L = levels("LA")
+    F3 = env.F.setdefault(3, torch.empty((rc.M, 3), dtype=torch.float64, device="cuda"))
+    F3.copy_(dev(rc.lag_values(30, 3)))
+    ctx = le.Context(0)
+    lvl = L.make(le, ctx, "X0")
+
+    def run():
+        Q = torch.full((rc.M, 3), SENT, dtype=torch.float64, device="cuda")
+        lvl.interp("side", L.u, Q, L.X["X0"])
+        f = [g.alloc("side") for g in L.geoms]
+        lvl.spread("side", f, F3, L.X["X0"])
+        ctx.synchronize()
+        return [Q] + [a for per in f for a in per]
+
+    kept = run()
+    assert bool((kept[0] != SENT).any()) and any(bool(a.any()) for a in kept[1:])
+    g0 = L.geoms[0]
+    wide = le.Geometry([0, 0, 0], [69999, 3, 3], g0.gcw, g0.dx, [0.0, 0.0, 0.0])
+    idx, xs, off = L.ghost
+    n = off[1]
+    with pytest.raises(IBTKLEError, match="too wide for 16-bit") as e:
+        le.Level.from_flat(ctx, [g0, wide], rc.LEVEL_KERNEL, L.X["X0"], idx[:n], xs[:n], [0, n, n], markers=lvl.markers)
+    assert e.value.code == 7
+    again = run()
+    assert len(again) == len(kept)
+    for i, (a, b) in enumerate(zip(again, kept)):
+        assert torch.equal(a, b), f"output {i} changed after the refused binning"
+    lvl.markers.close()
+    ctx.close()
